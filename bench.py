@@ -7,8 +7,16 @@ K3 SmartEncoding intern -> K4 string-pool gather -> K5 1s metric rollup),
 plus (world_size > 1) the RCCL dictionary-delta all-gather. Weak scaling:
 per-GPU work is fixed as N grows; every rank ingests a disjoint span range.
 
-Usage: python bench.py --gpus N --steps K --warmup W
+Usage: python bench.py --gpus N --steps K --warmup W [--full]
+                       [--dump-outputs DIR]
 Launched multi-GPU by the driver via torch.distributed.run (one rank/GPU).
+
+A plain run sets up, warms up, times the K steps and prints the result
+line. --full adds the measurements that need work of their own after the
+timed steps: the SmartEncoding byte accounting and the resident
+bytes/span after demoting to the two-tier store. --dump-outputs DIR
+writes what the last timed step stored (see dump_outputs) as
+DIR/<name>.npy so two builds can be compared output for output.
 """
 from __future__ import annotations
 
@@ -180,6 +188,98 @@ def smart_encoding_accounting(pipe, sample_rows: int = 50_000) -> dict:
             naive_all / max(smart_all, 1), 2),
         "accounting_sample_rows": n,
     }
+
+
+# --dump-outputs sizes: a fixed seeded row sample of the last batch, the
+# string pool of its first rows, and the head of the 1s rollup (all
+# together well under 64 MB as float32/float64)
+DUMP_SAMPLE_ROWS = 32768
+DUMP_POOL_ROWS = 8192
+DUMP_POOL_BYTES = 2 << 20
+DUMP_ROLLUP_GROUPS = 65536
+DUMP_SEED = 20240229
+
+
+def _split_u64(a: np.ndarray) -> np.ndarray:
+    """64-bit ints [...] -> float64 [..., 2] = (high, low) 32-bit halves
+    (float64 holds 32-bit values exactly; a raw cast would round)."""
+    u = np.ascontiguousarray(a).astype(np.int64).view(np.uint64)
+    return np.stack(((u >> np.uint64(32)).astype(np.float64),
+                     (u & np.uint64(0xFFFFFFFF)).astype(np.float64)),
+                    axis=-1)
+
+
+def dump_outputs(pipe, n_last: int, out_dir: str, suffix: str = "") -> None:
+    """Write what the last ingest step stored, as <out_dir>/<name>.npy.
+
+    The caller of the ingest path receives the batch as rows of the tail
+    segment plus the updated rollup table, so that is what is dumped:
+    the fixed-width columns, string lengths/refs and attr index of a
+    fixed seeded sample of the batch's rows, the pooled string bytes of
+    its first rows (when the batch has any), and the head of the application.1s rollup in key
+    order. Dictionary ids are slot indices of a table filled by racing
+    threads, so two runs may number the same string differently; they
+    are dumped as the slot's 64-bit string hash, which does not depend
+    on the insertion order. 64-bit values are split into exact 32-bit
+    halves (_split_u64)."""
+    os.makedirs(out_dir, exist_ok=True)
+    seg = pipe.segments.segments[-1]
+    base = seg.n_rows - n_last
+    assert n_last > 0 and base >= 0, (seg.n_rows, n_last)
+    dev = seg.u64.device
+    rng = np.random.default_rng(DUMP_SEED)
+    idx = np.sort(rng.choice(n_last, size=min(n_last, DUMP_SAMPLE_ROWS),
+                             replace=False)).astype(np.int64)
+    rows = torch.from_numpy(base + idx).to(dev)
+    tkeys = pipe.dict.tkeys
+
+    def id_hashes(ids: torch.Tensor) -> np.ndarray:
+        ids = ids.to(torch.int64)
+        ok = (ids >= 0) & (ids < tkeys.numel())
+        h = tkeys[ids.clamp(0, tkeys.numel() - 1)]
+        return _split_u64(torch.where(ok, h, torch.zeros_like(h))
+                          .cpu().numpy())
+
+    out = {
+        "sample_rows": idx.astype(np.float64),
+        "u64": _split_u64(seg.u64[:, rows].cpu().numpy()),
+        "u32": seg.u32[:, rows].cpu().numpy().view(np.uint32)
+        .astype(np.float64),
+        "u8": seg.u8[:, rows].cpu().numpy().astype(np.float32),
+        "str_lens": seg.str_lens[:, rows].cpu().numpy().astype(np.float32),
+        "str_rowref": _split_u64(seg.str_rowref[rows].cpu().numpy()),
+        "did_hash": id_hashes(seg.did[:, rows]),
+    }
+    # custom attrs: 2*cnt ids per row (names then values), rows in order
+    a_start = seg.attr_start[rows].cpu().numpy().astype(np.int64)
+    a_cnt = seg.attr_cnt[rows].cpu().numpy().astype(np.int64) * 2
+    out["attr_index"] = np.stack((a_start, a_cnt), axis=-1) \
+        .astype(np.float64)
+    total = int(a_cnt.sum())
+    flat = np.arange(total, dtype=np.int64) + \
+        np.repeat(a_start - (np.cumsum(a_cnt) - a_cnt), a_cnt)
+    assert total == 0 or (0 <= flat.min() and
+                          flat.max() < seg.attr_pool_len), "attr index"
+    out["attr_hash"] = id_hashes(seg.attr_pool[torch.from_numpy(flat).to(dev)])
+    # pooled strings of the batch's first rows (one contiguous region)
+    p = min(n_last, DUMP_POOL_ROWS)
+    off0 = (int(seg.str_rowref[base]) & ((1 << 64) - 1)) >> 16
+    off1 = seg.pool_len if p == n_last else \
+        (int(seg.str_rowref[base + p]) & ((1 << 64) - 1)) >> 16
+    off1 = min(off1, off0 + DUMP_POOL_BYTES, seg.pool_len)
+    out["pool_head"] = seg.pool[off0:max(off0, off1)].cpu().numpy() \
+        .astype(np.float32)
+    keys, vals = pipe.metrics._all_groups_np()
+    out["rollup_application_1s"] = np.concatenate(
+        (keys[:DUMP_ROLLUP_GROUPS], vals[:DUMP_ROLLUP_GROUPS]), axis=1) \
+        .astype(np.float64)
+    for name, arr in out.items():
+        if arr.size == 0:
+            # nothing of this kind stored (the synthetic spans carry no
+            # pooled strings, --n-attrs 0 no attrs): no file, not an
+            # empty one
+            continue
+        np.save(os.path.join(out_dir, f"{name}{suffix}.npy"), arr)
 
 
 def e2e_main(args) -> None:
@@ -403,7 +503,18 @@ def main() -> None:
     ap.add_argument("--path", default="direct", choices=["direct", "e2e"],
                     help="direct = pre-staged batches (headline); "
                          "e2e = loopback TCP receiver-fed ingest")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the SmartEncoding byte accounting and "
+                         "the two-tier demotion for resident bytes/span "
+                         "(extra work after the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step stored as "
+                         "DIR/<name>.npy (direct path)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.path != "direct":
+        ap.error("--dump-outputs applies to --path direct")
     if args.path == "e2e":
         e2e_main(args)
         return
@@ -513,18 +624,19 @@ def main() -> None:
                     state["routed"] = False
                     globals()["_route_failed"] = True
                     nonlocal_router[0] = None
-                    pipe.ingest_device(*dev_batch, host_payload)
+                    n_in = pipe.ingest_device(*dev_batch, host_payload)
                 else:
                     # harvest reads only the emitted slices from the
                     # device payload (no full-batch D2H when routed)
-                    pipe.ingest_device(pay, offs_t, lens_t, pay)
+                    n_in = pipe.ingest_device(pay, offs_t, lens_t, pay)
             else:
-                pipe.ingest_device(*dev_batch, host_payload)
+                n_in = pipe.ingest_device(*dev_batch, host_payload)
         else:
             payload, offs, lens = batches[i % n_distinct][:3]
             if nonlocal_router[0] is not None and device == "cpu":
                 payload, offs, lens = router.route_cpu(payload, offs, lens)
-            pipe.ingest(payload, offs, lens)
+            n_in = pipe.ingest(payload, offs, lens)
+        state["last_n"] = n_in  # rows of the newest batch (--dump-outputs)
         if dict_sync is not None:
             dict_sync.sync_step()
 
@@ -557,14 +669,20 @@ def main() -> None:
     bytes_per_span = seg.stored_bytes_per_row()
     if hasattr(pipe, "sync_stats"):
         pipe.sync_stats()  # land the deferred final-batch harvest
-    acct = smart_encoding_accounting(pipe, sample_rows=50_000)
-    # resident bytes/span with the two-tier store in steady state: all
-    # but the active tail segment bit-packed (demotion runs off the timed
-    # path, like the reference's background merges)
-    while pipe.segments.demote_oldest():
-        pass
-    n_all = max(pipe.segments.n_rows, 1)
-    resident = pipe.segments.total_stored_bytes() / n_all
+    if args.dump_outputs:
+        dump_outputs(pipe, state["last_n"], args.dump_outputs,
+                     suffix=f"_rank{rank}" if world > 1 else "")
+    acct = {}
+    resident = None
+    if args.full:
+        acct = smart_encoding_accounting(pipe, sample_rows=50_000)
+        # resident bytes/span with the two-tier store in steady state: all
+        # but the active tail segment bit-packed (demotion runs off the
+        # timed path, like the reference's background merges)
+        while pipe.segments.demote_oldest():
+            pass
+        n_all = max(pipe.segments.n_rows, 1)
+        resident = round(pipe.segments.total_stored_bytes() / n_all, 1)
 
     if rank == 0:
         out = {
@@ -591,7 +709,9 @@ def main() -> None:
                 "(UNROUTED fallback — routing failed)"),
                 "tag_cardinality": args.tag_card,
                 "bytes_per_span_stored": round(bytes_per_span, 1),
-                "bytes_per_span_resident": round(resident, 1),
+                # resident bytes and the SmartEncoding accounting are
+                # measured only with --full (null / absent otherwise)
+                "bytes_per_span_resident": resident,
                 # headline ratio = the tag scope the reference's 10x
                 # claim addresses (universal + custom tags)
                 "smart_encoding_ratio": acct.get(

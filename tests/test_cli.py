@@ -95,6 +95,11 @@ def test_agent_run_live(tmp_path):
     import time
     import threading
     from deepflow_amd.server import DeepflowServer
+    # the agent captures with an AF_PACKET socket, which needs CAP_NET_RAW
+    try:
+        socket.socket(socket.AF_PACKET, socket.SOCK_RAW, 0).close()
+    except OSError as e:
+        pytest.skip(f"AF_PACKET capture not permitted here ({e})")
     srv = DeepflowServer(device="cpu", tcp_port=0, segment_rows=1 << 10,
                          dict_capacity=1 << 12, time_base_s=0)
     srv.start()

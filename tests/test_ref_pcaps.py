@@ -1,20 +1,15 @@
-"""Replay the reference's golden pcap fixtures through the C++ agent engine
-(reads fixtures from the read-only reference mount when present; skipped on
-machines without it, e.g. GPU boxes). This validates our parsers against
-real captures, the reference's own test corpus
-(agent/resources/test/flow_generator)."""
+"""Replay the reference's golden pcap fixtures through the C++ agent engine.
+This validates our parsers against real captures from the reference's own
+test corpus (agent/resources/test/flow_generator); the captures the tests
+use are stored under tests/golden/flow_generator."""
 import os
 import struct
-
-import pytest
 
 from deepflow_amd.agent import Agent
 from deepflow_amd.wire import pb, flow_log, framing
 
-FIX = "/root/reference/agent/resources/test/flow_generator"
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(FIX),
-                                reason="reference fixtures not mounted")
+FIX = os.path.join(os.path.dirname(os.path.abspath(__file__)),
+                   "golden", "flow_generator")
 
 
 def read_pcap(path):
@@ -91,7 +86,7 @@ def test_redis_pcap():
 
 def test_mysql_pcap():
     path = f"{FIX}/mysql"
-    caps = [f for f in os.listdir(path) if f.endswith(".pcap")]
+    caps = sorted(f for f in os.listdir(path) if f.endswith(".pcap"))
     hits = 0
     for c in caps[:6]:
         l7, _, _ = replay(f"{path}/{c}")

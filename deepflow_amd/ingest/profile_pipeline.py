@@ -47,34 +47,85 @@ class ProfileStore:
         return len(self.rows) * 40 + sum(len(s) for s in self.id_to_loc)
 
 
+def _decompress(data: bytes) -> bytes:
+    import numpy as np
+    from ..ops import native
+    lib = native.cpu()
+    src = np.frombuffer(data, dtype=np.uint8)
+    dst = np.zeros(max(len(data) * 20, 1 << 16), dtype=np.uint8)
+    m = lib.df_zstd_decompress(src.ctypes.data, len(src),
+                               dst.ctypes.data, len(dst))
+    return dst[:m].tobytes() if m > 0 else b""
+
+
+def _is_folded(fmt: str) -> bool:
+    return fmt == "folded" or "folded" in fmt or fmt == ""
+
+
 class ProfilePipeline:
-    def __init__(self, counter: Optional[Counter] = None):
-        self.store = ProfileStore()
+    """device="cpu": the host ProfileStore (default, and the oracle for the
+    GPU path). device="cuda": a store.profile_store.GpuProfileStore; every
+    payload becomes one batch for the ingest kernel."""
+
+    def __init__(self, counter: Optional[Counter] = None,
+                 device: str = "cpu", stack_capacity: int = 1 << 20):
+        self.device = device
+        self.gpu = not str(device).startswith("cpu")
+        if self.gpu:
+            from ..store.profile_store import GpuProfileStore
+            self.store = GpuProfileStore(device=device,
+                                         stack_capacity=stack_capacity)
+        else:
+            self.store = ProfileStore()
         self.counter = counter or Counter("ingester.profile")
 
     def ingest_payload(self, payload: bytes) -> int:
         n = 0
-        for rec in framing.iter_records(bytes(payload)):
-            d = pb.decode(rec, metric.PROFILE)
-            self.ingest_profile(d)
-            n += 1
+        if self.gpu:
+            msgs = [pb.decode(rec, metric.PROFILE)
+                    for rec in framing.iter_records(bytes(payload))]
+            self._ingest_gpu(msgs)
+            n = len(msgs)
+        else:
+            for rec in framing.iter_records(bytes(payload)):
+                d = pb.decode(rec, metric.PROFILE)
+                self.ingest_profile(d)
+                n += 1
         self.counter.add("profiles_in", n)
         return n
+
+    def _ingest_gpu(self, msgs: List[Dict]) -> None:
+        """Whole payload -> one GpuProfileStore.ingest_batch call."""
+        blobs, metas = [], []
+        for d in msgs:
+            data = d.get("data", b"")
+            if d.get("data_compressed"):
+                data = _decompress(data)
+            folded = _is_folded(d.get("format", ""))
+            if folded:
+                count = d.get("count") or d.get("wide_count") or 1
+            else:
+                count = d.get("count", 1)
+            blobs.append(bytes(data))
+            metas.append({
+                "ts": d.get("timestamp") or (d.get("from_time", 0)
+                                             * 1_000_000),
+                "count": count, "folded": folded,
+                "series": (d.get("event_type", 0), d.get("pid", 0),
+                           d.get("tid", 0), d.get("pod_id", 0),
+                           d.get("process_name", ""), d.get("name", ""),
+                           d.get("spy_name", ""))})
+        self.store.ingest_batch(blobs, metas)
 
     def ingest_profile(self, d: Dict) -> None:
         """One Profile message. `data` holds the folded stack (eBPF mode) or
         a pyroscope-format blob (external push; collapsed lines)."""
+        if self.gpu:
+            self._ingest_gpu([d])
+            return
         data = d.get("data", b"")
         if d.get("data_compressed"):
-            import ctypes as ct
-            import numpy as np
-            from ..ops import native
-            lib = native.cpu()
-            src = np.frombuffer(data, dtype=np.uint8)
-            dst = np.zeros(max(len(data) * 20, 1 << 16), dtype=np.uint8)
-            m = lib.df_zstd_decompress(src.ctypes.data, len(src),
-                                       dst.ctypes.data, len(dst))
-            data = dst[:m].tobytes() if m > 0 else b""
+            data = _decompress(data)
         fmt = d.get("format", "")
         common = dict(
             event_type=d.get("event_type", 0),
@@ -85,7 +136,7 @@ class ProfilePipeline:
             profile_language_type=d.get("spy_name", ""),
         )
         ts = d.get("timestamp") or (d.get("from_time", 0) * 1_000_000)
-        if fmt == "folded" or "folded" in fmt or fmt == "":
+        if _is_folded(fmt):
             # one or more "stack;frames count" lines (collapsed format)
             count = d.get("count") or d.get("wide_count") or 1
             if b"\n" in data or b" " in data.strip():
@@ -104,9 +155,40 @@ class ProfilePipeline:
             self._add(ts, data, d.get("count", 1), common)
 
     def _add(self, ts: int, stack: bytes, value: int, common: Dict) -> None:
+        if self.gpu:
+            # one verbatim stack (the GPU profilers add samples this way)
+            from ..store.profile_store import SERIES_FIELDS
+            self.store.ingest_batch([bytes(stack)], [{
+                "ts": ts, "count": value, "folded": False,
+                "series": tuple(common[f] for f in SERIES_FIELDS)}])
+            return
         lid = self.store.intern(stack)
         self.store.rows.append(ProfileRow(
             timestamp=ts, location_id=lid, value=value, **common))
+
+    def flame(self, event_type: Optional[int] = None,
+              process_name: Optional[str] = None,
+              time_start: int = 0, time_end: int = 1 << 62) -> Dict:
+        """Flame tree over whichever store this pipeline owns. The GPU
+        store orders siblings by (-value, name); the host path by -value
+        with ties in first-seen order."""
+        if self.gpu:
+            return self.store.flame(event_type=event_type,
+                                    process_name=process_name,
+                                    time_start=time_start,
+                                    time_end=time_end)
+        return build_flame(self.store.rows, self.store.id_to_loc,
+                           event_type=event_type, process_name=process_name,
+                           time_start=time_start, time_end=time_end)
+
+    def processes(self) -> List[str]:
+        if self.gpu:
+            return self.store.processes()
+        return sorted({r.process_name for r in self.store.rows})
+
+    @property
+    def n_rows(self) -> int:
+        return self.store.n_rows if self.gpu else len(self.store.rows)
 
 
 def build_flame(rows: List[ProfileRow], id_to_loc: List[bytes],
@@ -152,12 +234,13 @@ class ProfileApp:
 
     def register(self, app) -> None:
         @app.get("/v1/profile/flame")
-        def flame(process_name: str = None, event_type: int = None):
-            st = self.pipe.store
-            return build_flame(st.rows, st.id_to_loc,
-                               event_type=event_type,
-                               process_name=process_name)
+        def flame(process_name: str = None, event_type: int = None,
+                  time_start: int = 0, time_end: int = 1 << 62):
+            return self.pipe.flame(event_type=event_type,
+                                   process_name=process_name,
+                                   time_start=time_start,
+                                   time_end=time_end)
 
         @app.get("/v1/profile/processes")
         def processes():
-            return sorted({r.process_name for r in self.pipe.store.rows})
+            return self.pipe.processes()

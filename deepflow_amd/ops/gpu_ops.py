@@ -240,3 +240,55 @@ def query_select(seg, spec_bytes: bytes, base_row: int, n: int,
         ctypes.addressof(buf), n, base_row,
         out_rows.data_ptr(), out_ctr.data_ptr(), out_rows.numel(), _stream()),
         "df_query_select")
+
+
+# ----------------------------------------------------------------------
+# K9: profile store ingest + flame fold (dfprofile.hip). `st` is a
+# store.profile_store.GpuProfileStore (owns every tensor named here).
+# ----------------------------------------------------------------------
+
+def prof_ingest(buf: torch.Tensor, line_off: torch.Tensor,
+                line_len: torch.Tensor, line_msg: torch.Tensor,
+                msg_ts: torch.Tensor, msg_count: torch.Tensor,
+                msg_series: torch.Tensor, msg_parse: torch.Tensor,
+                st, base_row: int) -> None:
+    lib = native.gpu()
+    native.check(lib.df_prof_ingest(
+        buf.data_ptr(), line_off.data_ptr(), line_len.data_ptr(),
+        line_msg.data_ptr(), line_off.numel(),
+        msg_ts.data_ptr(), msg_count.data_ptr(), msg_series.data_ptr(),
+        msg_parse.data_ptr(),
+        st.tkeys.data_ptr(), st.tkeys.numel(), st.stack_off.data_ptr(),
+        st.stack_len.data_ptr(), st.stack_frames.data_ptr(),
+        st.pool.data_ptr(), st.pool.numel(), st.pool_len.data_ptr(),
+        st.drops.data_ptr(),
+        st.row_ts.data_ptr(), st.row_val.data_ptr(),
+        st.row_stack.data_ptr(), st.row_series.data_ptr(), base_row,
+        _stream()), "df_prof_ingest")
+
+
+def prof_stack_sums(st, n_rows: int, series_ok: torch.Tensor,
+                    time_start: int, time_end: int, sums: torch.Tensor,
+                    hit: torch.Tensor, total: torch.Tensor) -> None:
+    lib = native.gpu()
+    native.check(lib.df_prof_stack_sums(
+        st.row_ts.data_ptr(), st.row_val.data_ptr(),
+        st.row_stack.data_ptr(), st.row_series.data_ptr(), n_rows,
+        series_ok.data_ptr(), series_ok.numel(), time_start, time_end,
+        sums.numel(), sums.data_ptr(), hit.data_ptr(), total.data_ptr(),
+        _stream()), "df_prof_stack_sums")
+
+
+def prof_flame_fold(st, hit: torch.Tensor, sums: torch.Tensor,
+                    nkeys: torch.Tensor, nparent: torch.Tensor,
+                    noff: torch.Tensor, nlen: torch.Tensor,
+                    ndepth: torch.Tensor, ntotal: torch.Tensor,
+                    nself: torch.Tensor, ndrops: torch.Tensor) -> None:
+    lib = native.gpu()
+    native.check(lib.df_prof_flame_fold(
+        hit.data_ptr(), sums.data_ptr(), st.stack_off.data_ptr(),
+        st.stack_len.data_ptr(), st.pool.data_ptr(), sums.numel(),
+        nkeys.data_ptr(), nparent.data_ptr(), noff.data_ptr(),
+        nlen.data_ptr(), ndepth.data_ptr(), ntotal.data_ptr(),
+        nself.data_ptr(), ndrops.data_ptr(), nkeys.numel(), _stream()),
+        "df_prof_flame_fold")

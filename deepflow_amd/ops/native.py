@@ -151,6 +151,20 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_pack_bits.argtypes = [p, u32, u32, u32, p, u32, u64]
     lib.df_unpack_bits.restype = ct.c_int
     lib.df_unpack_bits.argtypes = [p, u32, u32, u32, p, u64]
+    # K9 profile store / flame fold (dfprofile.hip)
+    i64 = ct.c_int64
+    lib.df_prof_root_key.restype = u64
+    lib.df_prof_root_key.argtypes = []
+    lib.df_prof_ingest.restype = ct.c_int
+    lib.df_prof_ingest.argtypes = [p, p, p, p, u32, p, p, p, p,
+                                   p, u32, p, p, p, p, u64, p, p,
+                                   p, p, p, p, u64, u64]
+    lib.df_prof_stack_sums.restype = ct.c_int
+    lib.df_prof_stack_sums.argtypes = [p, p, p, p, u64, p, u32, i64, i64,
+                                       u32, p, p, p, u64]
+    lib.df_prof_flame_fold.restype = ct.c_int
+    lib.df_prof_flame_fold.argtypes = [p, p, p, p, p, u32,
+                                       p, p, p, p, p, p, p, p, u32, u64]
 
 
 def gpu() -> ct.CDLL:

@@ -46,10 +46,7 @@ class McpServer:
         self.profiles = profile_pipeline
 
     def _tool_profile(self, args: Dict) -> str:
-        from ..ingest.profile_pipeline import build_flame
-        st = self.profiles.store
-        tree = build_flame(st.rows, st.id_to_loc,
-                           process_name=args.get("process_name"))
+        tree = self.profiles.flame(process_name=args.get("process_name"))
         flat = []
 
         def walk(node, path):

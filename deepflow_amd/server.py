@@ -31,7 +31,8 @@ class DeepflowServer:
                  time_base_s: int = 1_700_000_000,
                  platform_cfg: Optional[SpanGenConfig] = None,
                  native_pump: bool = False,
-                 pump_port: int = 0):
+                 pump_port: int = 0,
+                 gpu_profiles: bool = False):
         self.device = device
         self.kg = KnowledgeGraphTable(device=device)
         if platform_cfg is not None:
@@ -81,7 +82,12 @@ class DeepflowServer:
                                    raw_sources=[self.prom.series_for],
                                    sql_engine=self.engine)
         from .ingest.profile_pipeline import ProfilePipeline, ProfileApp
-        self.profiles = ProfilePipeline()
+        # gpu_profiles: keep the profile store in HBM and fold flame
+        # graphs with HIP kernels (store/profile_store.py); off by default
+        if gpu_profiles and not str(device).startswith("cpu"):
+            self.profiles = ProfilePipeline(device=device)
+        else:
+            self.profiles = ProfilePipeline()
         self.receiver.register(framing.MSG_PROFILE,
                                lambda hdr, payload:
                                self.profiles.ingest_payload(payload.tobytes()))
@@ -203,7 +209,7 @@ class DeepflowServer:
             with gp.capture():
                 _t.sleep(min(seconds, 10.0))
             return {"status": "ok",
-                    "rows": len(self.profiles.store.rows)}
+                    "rows": self.profiles.n_rows}
 
         @self.app.post("/v1/datasources/")
         async def add_datasource(request: Request):

@@ -98,20 +98,10 @@ DEV void skip_field(const uint8_t* p, uint32_t& pos, uint32_t end, uint32_t wt) 
     }
 }
 
-// parse 16 lowercase/uppercase hex chars at pos -> u64; false on non-hex
+// parse 16 hex chars at pos -> u64; false on non-hex (parser: dfhash.h)
 DEV bool hex_parse64(ByteStream& bs, uint32_t pos, uint64_t& out) {
-    uint64_t v = 0;
-    for (uint32_t i = 0; i < 16; i++) {
-        uint8_t c = bs.get(pos + i);
-        uint8_t d;
-        if (c >= '0' && c <= '9') d = c - '0';
-        else if (c >= 'a' && c <= 'f') d = c - 'a' + 10;
-        else if (c >= 'A' && c <= 'F') d = c - 'A' + 10;
-        else return false;
-        v = (v << 4) | d;
-    }
-    out = v;
-    return true;
+    return hex_parse64_with(
+        [&](uint32_t i) -> uint8_t { return bs.get(pos + i); }, out);
 }
 
 // ----------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // Device hash helpers shared by the HIP translation units of libdfgpu.so
-// (dfgpu.hip, dfprofile.hip). Internal linkage: each unit gets its own copy.
+// (dfgpu.hip, dfprofile.hip, dftrace.hip). Internal linkage: each unit gets
+// its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -35,6 +36,25 @@ DEV uint64_t mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
     z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
     return z ^ (z >> 31);
+}
+
+// parse 16 lowercase/uppercase hex chars get(0)..get(15) -> u64; false on
+// non-hex. One parser for the decoder (ids on the wire) and the trace-tree
+// join (pooled parent ids), so both derive the same key from the same text.
+template <typename Get>
+DEV bool hex_parse64_with(Get get, uint64_t& out) {
+    uint64_t v = 0;
+    for (uint32_t i = 0; i < 16; i++) {
+        uint8_t c = get(i);
+        uint8_t d;
+        if (c >= '0' && c <= '9') d = c - '0';
+        else if (c >= 'a' && c <= 'f') d = c - 'a' + 10;
+        else if (c >= 'A' && c <= 'F') d = c - 'A' + 10;
+        else return false;
+        v = (v << 4) | d;
+    }
+    out = v;
+    return true;
 }
 
 }  // namespace

@@ -147,6 +147,7 @@ enum {
 // python twin l7_schema.POOL_POS, sync-tested)
 #define L7_POOL_TRACE_ID 2
 #define L7_POOL_SPAN_ID 3
+#define L7_POOL_PARENT_SPAN_ID 4
 
 #define DICT_ID_INVALID 0xFFFFFFFFu
 #define STR_REF_PACK(off, len) \

@@ -292,3 +292,46 @@ def prof_flame_fold(st, hit: torch.Tensor, sums: torch.Tensor,
         nlen.data_ptr(), ndepth.data_ptr(), ntotal.data_ptr(),
         nself.data_ptr(), ndrops.data_ptr(), nkeys.numel(), _stream()),
         "df_prof_flame_fold")
+
+
+# ----------------------------------------------------------------------
+# K10: trace-tree assembly + service trace map (dftrace.hip). `ws` is a
+# query.tracemap._GpuWorkspace (owns every tensor named here; ws.flat_ptrs
+# is a host u64 array of the flat-column pointers in TraceFlat order).
+# ----------------------------------------------------------------------
+
+def trace_extract(seg, base_row: int, time_start: int, time_end: int,
+                  ws) -> None:
+    lib = native.gpu()
+    native.check(lib.df_trace_extract(
+        seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr(),
+        seg.did.data_ptr(), seg.str_rowref.data_ptr(),
+        seg.str_lens.data_ptr(), seg.pool.data_ptr(), seg.capacity,
+        seg.n_rows, base_row, time_start, time_end,
+        ws.flat_ptrs.ctypes.data, ws.idx_keys.data_ptr(),
+        ws.idx_rows.data_ptr(), ws.drops.data_ptr(), ws.idx_cap,
+        _stream()), "df_trace_extract")
+
+
+def trace_link(ws) -> None:
+    lib = native.gpu()
+    native.check(lib.df_trace_link(
+        ws.flat_ptrs.ctypes.data, ws.idx_keys.data_ptr(),
+        ws.idx_rows.data_ptr(), ws.idx_cap, ws.n, ws.parent.data_ptr(),
+        ws.kind.data_ptr(), _stream()), "df_trace_link")
+
+
+def trace_depth(ws) -> None:
+    lib = native.gpu()
+    native.check(lib.df_trace_depth(
+        ws.tkey.data_ptr(), ws.parent.data_ptr(), ws.n,
+        ws.depth.data_ptr(), _stream()), "df_trace_depth")
+
+
+def trace_fold(ws) -> None:
+    lib = native.gpu()
+    native.check(lib.df_trace_fold(
+        ws.flat_ptrs.ctypes.data, ws.parent.data_ptr(), ws.kind.data_ptr(),
+        ws.depth.data_ptr(), ws.n, ws.tkeys.data_ptr(), ws.tvals.data_ptr(),
+        ws.tkeys.numel(), ws.ekeys.data_ptr(), ws.evals.data_ptr(),
+        ws.ekeys.numel(), ws.drops.data_ptr(), _stream()), "df_trace_fold")

@@ -165,6 +165,19 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_prof_flame_fold.restype = ct.c_int
     lib.df_prof_flame_fold.argtypes = [p, p, p, p, p, u32,
                                        p, p, p, p, p, p, p, p, u32, u64]
+    # K10 trace-tree assembly / service trace map (dftrace.hip)
+    lib.df_trace_max_hops.restype = u32
+    lib.df_trace_max_hops.argtypes = []
+    lib.df_trace_extract.restype = ct.c_int
+    lib.df_trace_extract.argtypes = [p, p, p, p, p, p, p, u64, u32, u32,
+                                     u64, u64, p, p, p, p, u32, u64]
+    lib.df_trace_link.restype = ct.c_int
+    lib.df_trace_link.argtypes = [p, p, p, u32, u32, p, p, u64]
+    lib.df_trace_depth.restype = ct.c_int
+    lib.df_trace_depth.argtypes = [p, p, u32, p, u64]
+    lib.df_trace_fold.restype = ct.c_int
+    lib.df_trace_fold.argtypes = [p, p, p, p, u32, p, p, u32, p, p, u32,
+                                  p, u64]
 
 
 def gpu() -> ct.CDLL:

@@ -29,6 +29,13 @@ def mix64(z: int) -> int:
     return (z ^ (z >> 31)) & M64
 
 
+def hex_parse64_py(raw: bytes):
+    """Twin of dfhash.h hex_parse64_with: 16 hex chars -> int, else None."""
+    if len(raw) != 16 or not all(c in _HEXSET for c in raw):
+        return None
+    return int(raw, 16)
+
+
 # ---------------------------------------------------------------- K1 decode
 
 _U64_IDX = {c: i for i, c in enumerate(S.U64_COLS)}

@@ -96,7 +96,47 @@ class DistributedTracer:
             })
         return result
 
+    # ------------------------------------------------- bulk assembly (K10)
+    def trace_map(self, time_start: Optional[int] = None,
+                  time_end: Optional[int] = None) -> Dict:
+        """Per-trace summaries and the service -> service edge table for
+        every trace with spans in [time_start, time_end] (ns, inclusive);
+        see query/tracemap.py."""
+        from .tracemap import TraceMapper
+        return TraceMapper(self.engine).trace_map(time_start, time_end)
+
+    def build_trace_trees(self, time_start: Optional[int] = None,
+                          time_end: Optional[int] = None) -> Dict:
+        """Upsert one `trace_tree` row per trace in the window (the same
+        six fields `assemble()` caches), replacing a row with the same
+        trace_id."""
+        tm = self.trace_map(time_start, time_end)
+        at = {r["trace_id"]: i for i, r in enumerate(self.tree_rows)}
+        for t in tm["traces"]:
+            row = {k: t[k] for k in ("time", "trace_id", "span_count",
+                                     "max_depth", "root_service",
+                                     "duration_us")}
+            i = at.get(t["trace_id"])
+            if i is None:
+                at[t["trace_id"]] = len(self.tree_rows)
+                self.tree_rows.append(row)
+            else:
+                self.tree_rows[i] = row
+        return {"traces": tm["trace_count"], "spans": tm["span_count"],
+                "drops": tm["drops"], "rows": len(self.tree_rows)}
+
     def register(self, app) -> None:
+        # fixed paths first: the parameterised route below would swallow them
+        @app.get("/v1/tracing/map")
+        def tracing_map(time_start: Optional[int] = None,
+                        time_end: Optional[int] = None):
+            return self.trace_map(time_start, time_end)
+
+        @app.post("/v1/tracing/trees/build")
+        def tracing_build(time_start: Optional[int] = None,
+                          time_end: Optional[int] = None):
+            return self.build_trace_trees(time_start, time_end)
+
         @app.get("/v1/tracing/{trace_id}")
         def tracing(trace_id: str):
             return self.assemble(trace_id)

@@ -3,24 +3,89 @@ rows with dict-encoded fields). Reference: server/ingester/app_log.
 
 Wire: MSG_APPLICATION_LOG / MSG_SYSLOG / MSG_AGENT_LOG frames carrying
 line-oriented or record payloads; OTLP logs arrive via the OTLP route.
+
+device="cpu" (default): one dict per line on the host; this store is also
+the oracle for the GPU one. device="cuda": store/log_store.py::GpuLogStore
+keeps the payload bytes and the row columns in HBM and answers search() and
+histogram() with HIP kernels (K11).
 """
 from __future__ import annotations
 
 import time
-from typing import Dict, List, Optional
+from typing import Dict, List, Optional, Sequence, Union
 
 from ..utils.stats import Counter
 
 SEVERITIES = {"debug": 7, "info": 6, "warn": 4, "warning": 4, "error": 3,
               "fatal": 2, "critical": 2}
 
+MAX_NEEDLES = 8
+MAX_HIST_BUCKETS = 4096
+
+_FOLD = {c: c + 32 for c in range(ord("A"), ord("Z") + 1)}
+
+
+def fold_ascii(s: str) -> str:
+    """Lower-case A-Z only (what the scan kernel does on bytes)."""
+    return s.translate(_FOLD)
+
+
+def norm_needles(substr: Union[str, Sequence[str]]) -> List[str]:
+    """search()'s substr argument -> the non-empty needles (an empty
+    needle matches every row, so it constrains nothing)."""
+    needles = [substr] if isinstance(substr, str) else list(substr)
+    if len(needles) > MAX_NEEDLES:
+        raise ValueError(f"at most {MAX_NEEDLES} needles")
+    for s in needles:
+        if not isinstance(s, str):
+            raise TypeError("needles are str")
+    return [s for s in needles if s]
+
+
+def hist_buckets(interval: int, time_start: int, time_end: int) -> int:
+    if interval < 1:
+        raise ValueError("interval must be >= 1")
+    if time_end < time_start:
+        return 0
+    n = (time_end - time_start) // interval + 1
+    if n > MAX_HIST_BUCKETS:
+        raise ValueError(f"window holds {n} buckets "
+                         f"(max {MAX_HIST_BUCKETS})")
+    return n
+
 
 class AppLogPipeline:
-    def __init__(self, counter: Optional[Counter] = None):
-        self.rows: List[Dict] = []
+    def __init__(self, counter: Optional[Counter] = None,
+                 device: str = "cpu", **store_kw):
+        self.device = device
+        self.gpu = not str(device).startswith("cpu")
+        self._rows: List[Dict] = []
         # SmartEncoding for repetitive fields
         self.app_interner: Dict[str, int] = {}
         self.counter = counter or Counter("ingester.app_log")
+        if self.gpu:
+            from ..store.log_store import GpuLogStore
+            self.store = GpuLogStore(device=device, **store_kw)
+        elif store_kw:
+            raise TypeError(f"unexpected arguments for the host store: "
+                            f"{sorted(store_kw)}")
+
+    @property
+    def rows(self) -> List[Dict]:
+        """Every stored row, oldest first. On the GPU store this is a full
+        materialisation (D2H of all columns and the pool): fine for the SQL
+        table and for tests, not something to call per request."""
+        return self.store.rows if self.gpu else self._rows
+
+    @rows.setter
+    def rows(self, value: List[Dict]) -> None:
+        if self.gpu:
+            raise AttributeError("rows of the GPU store are read-only")
+        self._rows = value
+
+    @property
+    def n_rows(self) -> int:
+        return self.store.n_rows if self.gpu else len(self._rows)
 
     def _intern(self, s: str) -> int:
         i = self.app_interner.get(s)
@@ -30,16 +95,24 @@ class AppLogPipeline:
         return i
 
     def ingest_lines(self, payload: bytes, agent_id: int = 0,
-                     log_type: str = "system") -> int:
+                     log_type: str = "system",
+                     now: Optional[int] = None) -> int:
         """Line format: '<ts> <severity> <app> <body...>' with graceful
-        fallback for free-form lines."""
+        fallback for free-form lines, which get the time `now` (None: the
+        wall clock)."""
+        if self.gpu:
+            n = self.store.ingest_lines(
+                payload, agent_id=agent_id, log_type=log_type,
+                now=int(time.time()) if now is None else now)
+            self.counter.add("logs_in", n)
+            return n
         n = 0
         for line in payload.splitlines():
             line = line.decode("utf-8", "replace").strip()
             if not line:
                 continue
             parts = line.split(" ", 3)
-            ts = int(time.time())
+            ts = int(time.time()) if now is None else now
             sev = 6
             app = ""
             body = line
@@ -48,7 +121,7 @@ class AppLogPipeline:
                 sev = SEVERITIES.get(parts[1].lower(), 6)
                 app = parts[2]
                 body = parts[3]
-            self.rows.append({
+            self._rows.append({
                 "time": ts,
                 "agent_id": agent_id,
                 "log_type": log_type,
@@ -63,20 +136,134 @@ class AppLogPipeline:
 
     def ingest_rows(self, rows: List[Dict]) -> int:
         """Append pre-converted rows (OTLP logs path)."""
+        if self.gpu:
+            n = self.store.ingest_rows(rows)
+            self.counter.add("logs_in", n)
+            return n
         for r in rows:
             app = r.get("app_service", "")
             r.setdefault("app_id", self._intern(app))
-            self.rows.append(r)
+            self._rows.append(r)
         self.counter.add("logs_in", len(rows))
         return len(rows)
 
-    def search(self, substr: str = "", severity_max: int = 7,
-               limit: int = 100) -> List[Dict]:
-        out = []
-        for r in reversed(self.rows):
-            if r["severity"] <= severity_max and \
-                    (not substr or substr in r["body"]):
+    # -------------------------------------------------------------- query
+    def _matcher(self, substr, severity_max, time_start, time_end,
+                 app_service, case_insensitive):
+        needles = norm_needles(substr)
+        if case_insensitive:
+            needles = [fold_ascii(s) for s in needles]
+
+        def match(r: Dict) -> bool:
+            if r["severity"] > severity_max:
+                return False
+            if time_start is not None and r["time"] < time_start:
+                return False
+            if time_end is not None and r["time"] > time_end:
+                return False
+            if app_service is not None and \
+                    r.get("app_service", "") != app_service:
+                return False
+            if needles:
+                body = fold_ascii(r["body"]) if case_insensitive \
+                    else r["body"]
+                for s in needles:
+                    if s not in body:
+                        return False
+            return True
+        return match
+
+    def search(self, substr: Union[str, Sequence[str]] = "",
+               severity_max: int = 7, limit: int = 100, *,
+               time_start: Optional[int] = None,
+               time_end: Optional[int] = None,
+               app_service: Optional[str] = None,
+               case_insensitive: bool = False) -> List[Dict]:
+        """Newest-inserted first, cut at `limit`. substr: one needle or up
+        to 8, all of which must occur in the body; time_start/time_end are
+        inclusive bounds on `time`; app_service is an exact match;
+        case_insensitive folds ASCII A-Z only, on both sides."""
+        if self.gpu:
+            return self.store.search(
+                substr, severity_max, limit, time_start=time_start,
+                time_end=time_end, app_service=app_service,
+                case_insensitive=case_insensitive)
+        match = self._matcher(substr, severity_max, time_start, time_end,
+                              app_service, case_insensitive)
+        out: List[Dict] = []
+        if limit <= 0:
+            return out
+        for r in reversed(self._rows):
+            if match(r):
                 out.append(r)
                 if len(out) >= limit:
                     break
         return out
+
+    def histogram(self, interval: int, time_start: int, time_end: int,
+                  substr: Union[str, Sequence[str]] = "",
+                  severity_max: int = 7, *,
+                  app_service: Optional[str] = None,
+                  case_insensitive: bool = False) -> List[Dict]:
+        """Log volume per (time bucket, severity) over [time_start,
+        time_end] for the rows search() would match: [{"time":
+        bucket_start, "severity": s, "count": c}, ...] sorted by (time,
+        severity), nonzero counts only. Severity is clamped to 0..7."""
+        n_buckets = hist_buckets(interval, time_start, time_end)
+        if self.gpu:
+            return self.store.histogram(
+                interval, time_start, time_end, substr, severity_max,
+                app_service=app_service, case_insensitive=case_insensitive)
+        match = self._matcher(substr, severity_max, time_start, time_end,
+                              app_service, case_insensitive)
+        counts: Dict[tuple, int] = {}
+        if n_buckets:
+            for r in self._rows:
+                if match(r):
+                    b = time_start + \
+                        (r["time"] - time_start) // interval * interval
+                    key = (b, min(max(r["severity"], 0), 7))
+                    counts[key] = counts.get(key, 0) + 1
+        return [{"time": t, "severity": s, "count": c}
+                for (t, s), c in sorted(counts.items())]
+
+
+class LogApp:
+    """HTTP surface: log search and the log-volume histogram. Works on
+    either store."""
+
+    def __init__(self, pipeline: AppLogPipeline):
+        self.pipe = pipeline
+
+    def register(self, app) -> None:
+        from fastapi import HTTPException, Query
+
+        def guarded(fn, *args, **kw):
+            try:
+                return fn(*args, **kw)
+            except ValueError as e:
+                raise HTTPException(status_code=400, detail=str(e))
+
+        @app.get("/v1/logs/search")
+        def logs_search(q: List[str] = Query(default=[]),
+                        severity_max: int = 7,
+                        time_start: Optional[int] = None,
+                        time_end: Optional[int] = None,
+                        app_service: Optional[str] = None,
+                        case_insensitive: bool = False,
+                        limit: int = 100):
+            return guarded(self.pipe.search, q, severity_max, limit,
+                           time_start=time_start, time_end=time_end,
+                           app_service=app_service,
+                           case_insensitive=case_insensitive)
+
+        @app.get("/v1/logs/histogram")
+        def logs_histogram(interval: int, time_start: int, time_end: int,
+                           q: List[str] = Query(default=[]),
+                           severity_max: int = 7,
+                           app_service: Optional[str] = None,
+                           case_insensitive: bool = False):
+            return guarded(self.pipe.histogram, interval, time_start,
+                           time_end, q, severity_max,
+                           app_service=app_service,
+                           case_insensitive=case_insensitive)

@@ -1,5 +1,5 @@
 // Device hash helpers shared by the HIP translation units of libdfgpu.so
-// (dfgpu.hip, dfprofile.hip, dftrace.hip). Internal linkage: each unit gets
+// (dfgpu.hip, dfprofile.hip, dftrace.hip, dflog.hip). Internal linkage: each unit gets
 // its own copy.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -1,0 +1,461 @@
+// dflog — K11: GPU-resident application-log store and substring search.
+//
+// Replaces the host path of ingest/applog_pipeline.py (one Python dict per
+// line, an interpreter loop over every stored row per search) with: raw
+// payload bytes kept in an HBM pool exactly as they arrived, thread-per-line
+// parsing into row columns, and a flat, bandwidth-bound scan of the pool per
+// query.
+//
+// Rules (same as dfgpu.hip / dfprofile.hip):
+//  - wave = 64 lanes; blocks are multiples of 64.
+//  - all cross-workgroup state uses device-scope atomics; no kernel reads
+//    in the same launch what another workgroup wrote with plain stores.
+//  - ids are SLOT INDICES: a claim is one atomicCAS on the 64-bit key. The
+//    claimer alone writes the slot's metadata and nobody reads it before
+//    the next launch.
+//  - probe loops are bounded by the table size; EMPTY_KEY = 0 is reserved.
+//  - 64-bit hash identity is accepted for app names as it is for every
+//    other dictionary here.
+//
+// Flat scan, not row scan: k_log_scan walks pool bytes, not rows. Bodies
+// are 0..kilobytes long; a thread-per-row matcher would diverge on length
+// and load each lane's bytes from an unrelated address. The flat scan
+// stages a fixed tile with 16-byte loads, tests every start position from
+// LDS and only maps the (rare) hits back to a row with a binary search over
+// body_off, which is non-decreasing in row index.
+#include <hip/hip_runtime.h>
+#include <string.h>
+#include "l7_layout.h"   // DICT_ID_INVALID
+
+#define DEV __device__ __forceinline__
+#include "dfhash.h"
+
+namespace {
+
+constexpr uint64_t EMPTY_KEY = 0ull;
+constexpr uint32_t BLOCK = 256;
+constexpr uint64_t LOG_APP_SEED = 0x4C4F474150504944ull;    // "LOGAPPID"
+
+constexpr uint32_t LOG_TILE = 16384;        // match start positions per block
+constexpr uint32_t LOG_MAX_NEEDLES = 8;
+constexpr uint32_t LOG_MAX_NEEDLE = 128;
+// staged bytes: tile + the longest needle's overhang, in whole 16-byte
+// chunks, so every LDS index the compare loop can form is initialised
+constexpr uint32_t LOG_STAGE_CHUNKS = (LOG_TILE + LOG_MAX_NEEDLE) / 16;
+// positions handled per block iteration: each lane owns one dword
+constexpr uint32_t LOG_STRIDE = BLOCK * 4;
+
+// histogram tables of up to this many (bucket, severity) cells are
+// pre-aggregated per block in LDS (16 KiB of u32 counters); larger ones,
+// up to 4096 buckets x 8, go straight to global atomics
+constexpr uint32_t LOG_HIST_LDS_CELLS = 4096;
+constexpr uint32_t LOG_HIST_LDS_BUCKETS = LOG_HIST_LDS_CELLS / 8;
+constexpr uint32_t LOG_SELECT_MAX_BLOCKS = 2048;
+
+DEV uint8_t fold_ascii(uint8_t c) {
+    return (c >= 'A' && c <= 'Z') ? (uint8_t)(c + 32) : c;
+}
+
+// four bytes at once: set 0x20 in every byte that is 'A'..'Z'
+DEV uint32_t fold_ascii4(uint32_t x) {
+    uint32_t t = x & 0x7f7f7f7fu;
+    uint32_t ge = t + 0x3f3f3f3fu;          // bit 7 set when byte >= 0x41
+    uint32_t gt = t + 0x25252525u;          // bit 7 set when byte >= 0x5b
+    uint32_t m = ge & ~gt & ~x & 0x80808080u;
+    return x | (m >> 2);
+}
+
+// probe-or-insert; returns slot, sets claimed when this thread inserted h
+DEV uint32_t log_probe(uint64_t h, uint64_t* tkeys, uint32_t cap_mask,
+                       bool& claimed) {
+    claimed = false;
+    uint32_t slot = (uint32_t)(h & cap_mask);
+    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
+        uint64_t cur = tkeys[slot];
+        if (cur == h) return slot;
+        if (cur == EMPTY_KEY) {
+            uint64_t old = atomicCAS((unsigned long long*)&tkeys[slot],
+                                     EMPTY_KEY, h);
+            if (old == EMPTY_KEY) { claimed = true; return slot; }
+            if (old == h) return slot;
+        }
+        slot = (slot + 1) & cap_mask;
+    }
+    return DICT_ID_INVALID;
+}
+
+template <uint32_t N>
+DEV bool word_is(const uint8_t* s, uint32_t len, const char (&w)[N]) {
+    if (len != N - 1) return false;
+    for (uint32_t i = 0; i < N - 1; i++)
+        if (fold_ascii(s[i]) != (uint8_t)w[i]) return false;
+    return true;
+}
+
+// SEVERITIES of ingest/applog_pipeline.py; anything else is 6 (info)
+DEV uint8_t severity_of(const uint8_t* s, uint32_t len) {
+    if (word_is(s, len, "debug")) return 7;
+    if (word_is(s, len, "info")) return 6;
+    if (word_is(s, len, "warn")) return 4;
+    if (word_is(s, len, "warning")) return 4;
+    if (word_is(s, len, "error")) return 3;
+    if (word_is(s, len, "fatal")) return 2;
+    if (word_is(s, len, "critical")) return 2;
+    return 6;
+}
+
+struct LogApps {
+    uint64_t* tkeys;          // [cap]
+    int64_t* app_off;         // [cap] offset of the claimer's token in pool
+    int32_t* app_len;         // [cap]
+    unsigned long long* drops;
+    uint32_t cap_mask;
+};
+
+struct LogRows {
+    int64_t* time;
+    uint8_t* severity;
+    uint32_t* agent_id;
+    uint16_t* log_type;
+    uint32_t* app_id;
+    int64_t* body_off;
+    int32_t* body_len;
+};
+
+// one thread per stripped, non-empty line. pool already holds the batch at
+// [base, ...); line_off is relative to base. pre_* == nullptr: parse
+// '<ts> <severity> <app> <body...>' as line.split(" ", 3) does. Otherwise
+// the line is app bytes followed by body bytes and pre_* carry the rest.
+__global__ void k_log_ingest(const uint8_t* __restrict__ pool, uint64_t base,
+                             const int64_t* __restrict__ line_off,
+                             const int32_t* __restrict__ line_len,
+                             uint32_t n_lines,
+                             const int32_t* __restrict__ pre_app_len,
+                             const int64_t* __restrict__ pre_time,
+                             const uint8_t* __restrict__ pre_sev,
+                             int64_t now, uint32_t agent_id,
+                             uint32_t log_type, LogApps apps, LogRows rows,
+                             uint64_t base_row) {
+    uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_lines) return;
+    uint64_t off = base + (uint64_t)line_off[i];
+    uint32_t len = (uint32_t)line_len[i];
+    const uint8_t* s = pool + off;
+
+    int64_t ts = now;
+    uint8_t sev = 6;
+    uint32_t a_at = 0, a_len = 0;       // app token, relative to the line
+    uint32_t b_at = 0;                  // body start, relative to the line
+    if (pre_app_len) {
+        a_len = (uint32_t)pre_app_len[i];
+        if (a_len > len) a_len = len;
+        b_at = a_len;
+        ts = pre_time[i];
+        sev = pre_sev[i];
+    } else {
+        uint32_t sp[3];
+        uint32_t found = 0;
+        for (uint32_t p = 0; p < len && found < 3; p++)
+            if (s[p] == 0x20) sp[found++] = p;
+        if (found == 3 && sp[0] >= 1 && sp[0] <= 18) {
+            uint64_t v = 0;
+            bool digits = true;
+            for (uint32_t p = 0; p < sp[0]; p++) {
+                uint8_t c = s[p];
+                if (c < '0' || c > '9') { digits = false; break; }
+                v = v * 10 + (c - '0');
+            }
+            if (digits) {
+                ts = (int64_t)v;
+                sev = severity_of(s + sp[0] + 1, sp[1] - sp[0] - 1);
+                a_at = sp[1] + 1;
+                a_len = sp[2] - sp[1] - 1;
+                b_at = sp[2] + 1;
+            }
+        }
+    }
+
+    uint64_t h = str_hash(s + a_at, a_len, LOG_APP_SEED);
+    bool claimed;
+    uint32_t aid = log_probe(h, apps.tkeys, apps.cap_mask, claimed);
+    if (aid == DICT_ID_INVALID) {
+        atomicAdd(apps.drops, 1ull);
+    } else if (claimed) {
+        apps.app_off[aid] = (int64_t)(off + a_at);
+        apps.app_len[aid] = (int32_t)a_len;
+    }
+
+    uint64_t row = base_row + i;
+    rows.time[row] = ts;
+    rows.severity[row] = sev;
+    rows.agent_id[row] = agent_id;
+    rows.log_type[row] = (uint16_t)log_type;
+    rows.app_id[row] = aid;
+    rows.body_off[row] = (int64_t)(off + b_at);
+    rows.body_len[row] = (int32_t)(len - b_at);
+}
+
+// needles of one query, passed by value as a kernel argument
+struct LogNeedles {
+    uint8_t bytes[LOG_MAX_NEEDLES][LOG_MAX_NEEDLE];
+    uint32_t len[LOG_MAX_NEEDLES];
+    uint32_t n;
+    uint32_t maxlen;
+};
+
+// last row in [lo, hi) whose body_off <= p, or -1
+DEV int64_t last_row_le(const int64_t* __restrict__ body_off, int64_t lo,
+                        int64_t hi, int64_t p) {
+    while (lo < hi) {
+        int64_t mid = lo + ((hi - lo) >> 1);
+        if (body_off[mid] <= p) lo = mid + 1; else hi = mid;
+    }
+    return lo - 1;
+}
+
+// Block b owns match starts in [scan_lo + b*TILE, scan_lo + (b+1)*TILE),
+// clipped at scan_hi. scan_lo is a multiple of 16 and the pool's capacity
+// is too, so every 16-byte load that starts below scan_hi is in bounds.
+__global__ __launch_bounds__(BLOCK)
+void k_log_scan(const uint8_t* __restrict__ pool, uint64_t scan_lo,
+                uint64_t scan_hi,
+                const int64_t* __restrict__ body_off,
+                const int32_t* __restrict__ body_len, uint64_t n_rows,
+                LogNeedles nd, uint32_t fold, uint32_t* __restrict__ mask) {
+    __shared__ uint4 s_tile4[LOG_STAGE_CHUNKS];
+    __shared__ uint8_t s_needle[LOG_MAX_NEEDLES][LOG_MAX_NEEDLE];
+    __shared__ uint32_t s_first[LOG_MAX_NEEDLES];
+    __shared__ uint32_t s_fmask[LOG_MAX_NEEDLES];
+    __shared__ int64_t s_rlo, s_rhi;
+
+    const uint32_t tid = threadIdx.x;
+    const uint64_t t0 = scan_lo + (uint64_t)blockIdx.x * LOG_TILE;
+    if (t0 >= scan_hi) return;                        // uniform per block
+    const uint64_t left = scan_hi - t0;
+    const uint32_t n_start = left < LOG_TILE ? (uint32_t)left : LOG_TILE;
+    const uint64_t want = (uint64_t)LOG_TILE + nd.maxlen - 1;
+    const uint32_t stage = left < want ? (uint32_t)left : (uint32_t)want;
+    const uint32_t chunks = (stage + 15) / 16;
+
+    const uint4* src = reinterpret_cast<const uint4*>(pool + t0);
+    for (uint32_t c = tid; c < LOG_STAGE_CHUNKS; c += BLOCK) {
+        uint4 v = make_uint4(0, 0, 0, 0);
+        if (c < chunks) {
+            v = src[c];
+            if (fold) {
+                v.x = fold_ascii4(v.x); v.y = fold_ascii4(v.y);
+                v.z = fold_ascii4(v.z); v.w = fold_ascii4(v.w);
+            }
+        }
+        s_tile4[c] = v;
+    }
+    for (uint32_t b = tid; b < LOG_MAX_NEEDLES * LOG_MAX_NEEDLE; b += BLOCK)
+        s_needle[b / LOG_MAX_NEEDLE][b % LOG_MAX_NEEDLE] =
+            nd.bytes[b / LOG_MAX_NEEDLE][b % LOG_MAX_NEEDLE];
+    if (tid < LOG_MAX_NEEDLES) {
+        uint32_t L = tid < nd.n ? nd.len[tid] : 0;
+        uint32_t w = 0, m = 0;
+        for (uint32_t b = 0; b < 4 && b < L; b++) {
+            w |= (uint32_t)nd.bytes[tid][b] << (8 * b);
+            m |= 0xffu << (8 * b);
+        }
+        s_first[tid] = w;
+        s_fmask[tid] = m;
+    }
+    if (tid == 0) {
+        // rows that can hold a byte of this tile: [s_rlo, s_rhi]
+        int64_t hi = last_row_le(body_off, 0, (int64_t)n_rows,
+                                 (int64_t)(t0 + n_start - 1));
+        int64_t lo = hi < 0 ? 0
+                   : last_row_le(body_off, 0, hi + 1, (int64_t)t0);
+        s_rlo = lo < 0 ? 0 : lo;
+        s_rhi = hi;
+    }
+    __syncthreads();
+    const int64_t rlo = s_rlo, rhi = s_rhi;
+    if (rhi < 0) return;                              // uniform per block
+
+    const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(s_tile4);
+    const uint8_t* tile8 = reinterpret_cast<const uint8_t*>(s_tile4);
+    const uint32_t n_needles = nd.n;
+
+    // the row of this thread's previous hit: tested first, so a dense
+    // needle does not pay a binary search per hit
+    int64_t cr = -1, c_lo = 0, c_hi = 0;
+
+    for (uint32_t it = 0; it * LOG_STRIDE < n_start; it++) {
+        uint32_t q0 = it * LOG_STRIDE + tid * 4;
+        if (q0 >= n_start) continue;
+        uint64_t w64 = (uint64_t)tile32[q0 / 4]
+                     | ((uint64_t)tile32[q0 / 4 + 1] << 32);
+        for (uint32_t j = 0; j < 4; j++) {
+            uint32_t q = q0 + j;
+            if (q >= n_start) break;
+            uint32_t w = (uint32_t)(w64 >> (8 * j));
+            for (uint32_t k = 0; k < n_needles; k++) {
+                if ((w & s_fmask[k]) != s_first[k]) continue;
+                uint32_t L = nd.len[k];
+                if (q + L > stage) continue;
+                bool eq = true;
+                for (uint32_t b = 4; b < L; b++)
+                    if (tile8[q + b] != s_needle[k][b]) { eq = false; break; }
+                if (!eq) continue;
+                int64_t p = (int64_t)(t0 + q);
+                if (!(cr >= 0 && c_lo <= p && p + (int64_t)L <= c_hi)) {
+                    int64_t r = last_row_le(body_off, rlo, rhi + 1, p);
+                    if (r < 0) continue;
+                    cr = r;
+                    c_lo = body_off[r];
+                    c_hi = c_lo + body_len[r];
+                    if (p + (int64_t)L > c_hi) continue;
+                }
+                uint32_t bit = 1u << k;
+                // a stale read only costs a redundant atomic
+                if (!(__atomic_load_n(&mask[cr], __ATOMIC_RELAXED) & bit))
+                    atomicOr(&mask[cr], bit);
+            }
+        }
+    }
+}
+
+// thread per row (grid-stride): filter flag + optional histogram
+__global__ __launch_bounds__(BLOCK)
+void k_log_select(const int64_t* __restrict__ time,
+                  const uint8_t* __restrict__ severity,
+                  const uint32_t* __restrict__ app_id,
+                  const uint32_t* __restrict__ mask, uint64_t n_rows,
+                  uint32_t severity_max, int64_t t_lo, int64_t t_hi,
+                  uint32_t use_app, uint64_t app_key,
+                  const uint64_t* __restrict__ tkeys, uint32_t app_cap,
+                  uint32_t need, uint8_t* __restrict__ flags,
+                  unsigned long long* __restrict__ hist, uint64_t interval,
+                  uint32_t n_buckets) {
+    __shared__ uint32_t s_hist[LOG_HIST_LDS_CELLS];
+    const bool in_lds = hist && n_buckets <= LOG_HIST_LDS_BUCKETS;
+    const uint32_t cells = n_buckets * 8;
+    if (in_lds) {
+        for (uint32_t c = threadIdx.x; c < cells; c += BLOCK) s_hist[c] = 0;
+        __syncthreads();
+    }
+    const uint64_t step = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+         r < n_rows; r += step) {
+        uint32_t sev = severity[r];
+        int64_t ts = time[r];
+        bool ok = sev <= severity_max && ts >= t_lo && ts <= t_hi
+                  && (mask[r] & need) == need;
+        if (ok && use_app) {
+            uint32_t a = app_id[r];
+            ok = a < app_cap && tkeys[a] == app_key;
+        }
+        flags[r] = ok ? 1 : 0;
+        if (ok && hist) {
+            uint64_t b = (uint64_t)(ts - t_lo) / interval;
+            if (b < n_buckets) {
+                uint32_t cell = (uint32_t)b * 8 + (sev > 7 ? 7 : sev);
+                if (in_lds) atomicAdd(&s_hist[cell], 1u);
+                else atomicAdd(&hist[cell], 1ull);
+            }
+        }
+    }
+    if (in_lds) {
+        __syncthreads();
+        for (uint32_t c = threadIdx.x; c < cells; c += BLOCK) {
+            uint32_t v = s_hist[c];
+            if (v) atomicAdd(&hist[c], (unsigned long long)v);
+        }
+    }
+}
+
+inline uint32_t grid_for(uint64_t total) {
+    return (uint32_t)((total + BLOCK - 1) / BLOCK);
+}
+
+}  // namespace
+
+#define STREAM(s) reinterpret_cast<hipStream_t>(s)
+
+extern "C" {
+
+uint32_t df_log_tile_bytes() { return LOG_TILE; }
+uint64_t df_log_app_seed() { return LOG_APP_SEED; }
+uint32_t df_log_hist_lds_buckets() { return LOG_HIST_LDS_BUCKETS; }
+
+int df_log_ingest(const void* pool, uint64_t base, const void* line_off,
+                  const void* line_len, uint32_t n_lines,
+                  const void* pre_app_len, const void* pre_time,
+                  const void* pre_sev, int64_t now, uint32_t agent_id,
+                  uint32_t log_type,
+                  void* tkeys, uint32_t cap, void* app_off, void* app_len,
+                  void* drops,
+                  void* row_time, void* row_sev, void* row_agent,
+                  void* row_type, void* row_app, void* row_boff,
+                  void* row_blen, uint64_t base_row, uint64_t stream) {
+    if (n_lines == 0) return 0;
+    LogApps apps{(uint64_t*)tkeys, (int64_t*)app_off, (int32_t*)app_len,
+                 (unsigned long long*)drops, cap - 1};
+    LogRows rows{(int64_t*)row_time, (uint8_t*)row_sev, (uint32_t*)row_agent,
+                 (uint16_t*)row_type, (uint32_t*)row_app, (int64_t*)row_boff,
+                 (int32_t*)row_blen};
+    hipLaunchKernelGGL(k_log_ingest, dim3(grid_for(n_lines)), dim3(BLOCK),
+                       0, STREAM(stream),
+                       (const uint8_t*)pool, base, (const int64_t*)line_off,
+                       (const int32_t*)line_len, n_lines,
+                       (const int32_t*)pre_app_len, (const int64_t*)pre_time,
+                       (const uint8_t*)pre_sev, now, agent_id, log_type,
+                       apps, rows, base_row);
+    return (int)hipGetLastError();
+}
+
+// needle_bytes: n_needles strings back to back, needle_len[k] bytes each
+// (host memory). Returns -1 for a needle list the kernel does not take.
+int df_log_scan(const void* pool, uint64_t scan_lo, uint64_t scan_hi,
+                const void* body_off, const void* body_len, uint64_t n_rows,
+                const void* needle_bytes, const uint32_t* needle_len,
+                uint32_t n_needles, uint32_t fold, void* mask,
+                uint64_t stream) {
+    if (n_needles == 0 || n_rows == 0 || scan_hi <= scan_lo) return 0;
+    if (n_needles > LOG_MAX_NEEDLES || (scan_lo & 15)) return -1;
+    LogNeedles nd;
+    memset(&nd, 0, sizeof(nd));
+    const uint8_t* src = (const uint8_t*)needle_bytes;
+    for (uint32_t k = 0; k < n_needles; k++) {
+        uint32_t L = needle_len[k];
+        if (L < 1 || L > LOG_MAX_NEEDLE) return -1;
+        memcpy(nd.bytes[k], src, L);
+        src += L;
+        nd.len[k] = L;
+        if (L > nd.maxlen) nd.maxlen = L;
+    }
+    nd.n = n_needles;
+    uint64_t blocks = (scan_hi - scan_lo + LOG_TILE - 1) / LOG_TILE;
+    hipLaunchKernelGGL(k_log_scan, dim3((uint32_t)blocks), dim3(BLOCK), 0,
+                       STREAM(stream), (const uint8_t*)pool, scan_lo,
+                       scan_hi, (const int64_t*)body_off,
+                       (const int32_t*)body_len, n_rows, nd, fold,
+                       (uint32_t*)mask);
+    return (int)hipGetLastError();
+}
+
+int df_log_select(const void* time, const void* severity,
+                  const void* app_id, const void* mask, uint64_t n_rows,
+                  uint32_t severity_max, int64_t t_lo, int64_t t_hi,
+                  uint32_t use_app, uint64_t app_key, const void* tkeys,
+                  uint32_t app_cap, uint32_t need, void* flags, void* hist,
+                  uint64_t interval, uint32_t n_buckets, uint64_t stream) {
+    if (n_rows == 0) return 0;
+    if (hist && (interval == 0 || n_buckets == 0 || n_buckets > 4096))
+        return -1;
+    uint32_t blocks = grid_for(n_rows);
+    if (blocks > LOG_SELECT_MAX_BLOCKS) blocks = LOG_SELECT_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_log_select, dim3(blocks), dim3(BLOCK), 0,
+                       STREAM(stream), (const int64_t*)time,
+                       (const uint8_t*)severity, (const uint32_t*)app_id,
+                       (const uint32_t*)mask, n_rows, severity_max, t_lo,
+                       t_hi, use_app, app_key, (const uint64_t*)tkeys,
+                       app_cap, need, (uint8_t*)flags,
+                       (unsigned long long*)hist, interval, n_buckets);
+    return (int)hipGetLastError();
+}
+
+}  // extern "C"

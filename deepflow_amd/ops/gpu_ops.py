@@ -335,3 +335,58 @@ def trace_fold(ws) -> None:
         ws.depth.data_ptr(), ws.n, ws.tkeys.data_ptr(), ws.tvals.data_ptr(),
         ws.tkeys.numel(), ws.ekeys.data_ptr(), ws.evals.data_ptr(),
         ws.ekeys.numel(), ws.drops.data_ptr(), _stream()), "df_trace_fold")
+
+
+# ----------------------------------------------------------------------
+# K11: application-log store + substring search (dflog.hip). `st` is a
+# store.log_store.GpuLogStore (owns every tensor named here).
+# ----------------------------------------------------------------------
+
+def log_ingest(st, base: int, line_off: torch.Tensor, line_len: torch.Tensor,
+               now: int, agent_id: int, log_type: int, base_row: int,
+               pre_app_len: torch.Tensor = None,
+               pre_time: torch.Tensor = None,
+               pre_sev: torch.Tensor = None) -> None:
+    """Parse (or, with pre_*, take as parsed) the lines of the batch that
+    already sits in st.pool at `base`; line_off is relative to it."""
+    lib = native.gpu()
+    pre = [t.data_ptr() if t is not None else 0
+           for t in (pre_app_len, pre_time, pre_sev)]
+    native.check(lib.df_log_ingest(
+        st.pool.data_ptr(), base, line_off.data_ptr(), line_len.data_ptr(),
+        line_off.numel(), pre[0], pre[1], pre[2], now, agent_id, log_type,
+        st.tkeys.data_ptr(), st.tkeys.numel(), st.app_off.data_ptr(),
+        st.app_len.data_ptr(), st.drops.data_ptr(),
+        st.row_time.data_ptr(), st.row_sev.data_ptr(),
+        st.row_agent.data_ptr(), st.row_type.data_ptr(),
+        st.row_app.data_ptr(), st.row_boff.data_ptr(),
+        st.row_blen.data_ptr(), base_row, _stream()), "df_log_ingest")
+
+
+def log_scan(st, needles, fold: bool, mask: torch.Tensor) -> None:
+    """OR bit k into mask[row] for every row whose body holds needles[k]
+    (bytes, 1..128 each, at most 8; already folded when fold is set)."""
+    import numpy as np
+    if not needles:
+        return
+    lib = native.gpu()
+    lens = np.array([len(x) for x in needles], dtype=np.uint32)
+    native.check(lib.df_log_scan(
+        st.pool.data_ptr(), 0, st.pool_len, st.row_boff.data_ptr(),
+        st.row_blen.data_ptr(), st.n_rows, b"".join(needles),
+        lens.ctypes.data, len(needles), 1 if fold else 0, mask.data_ptr(),
+        _stream()), "df_log_scan")
+
+
+def log_select(st, mask: torch.Tensor, need: int, severity_max: int,
+               t_lo: int, t_hi: int, app_key, flags: torch.Tensor,
+               hist: torch.Tensor = None, interval: int = 1,
+               n_buckets: int = 0) -> None:
+    lib = native.gpu()
+    native.check(lib.df_log_select(
+        st.row_time.data_ptr(), st.row_sev.data_ptr(),
+        st.row_app.data_ptr(), mask.data_ptr(), st.n_rows, severity_max,
+        t_lo, t_hi, 0 if app_key is None else 1, app_key or 0,
+        st.tkeys.data_ptr(), st.tkeys.numel(), need, flags.data_ptr(),
+        hist.data_ptr() if hist is not None else 0, interval, n_buckets,
+        _stream()), "df_log_select")

@@ -178,6 +178,23 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_trace_fold.restype = ct.c_int
     lib.df_trace_fold.argtypes = [p, p, p, p, u32, p, p, u32, p, p, u32,
                                   p, u64]
+    # K11 application-log store / substring search (dflog.hip)
+    lib.df_log_tile_bytes.restype = u32
+    lib.df_log_tile_bytes.argtypes = []
+    lib.df_log_app_seed.restype = u64
+    lib.df_log_app_seed.argtypes = []
+    lib.df_log_hist_lds_buckets.restype = u32
+    lib.df_log_hist_lds_buckets.argtypes = []
+    lib.df_log_ingest.restype = ct.c_int
+    lib.df_log_ingest.argtypes = [p, u64, p, p, u32, p, p, p, i64, u32, u32,
+                                  p, u32, p, p, p,
+                                  p, p, p, p, p, p, p, u64, u64]
+    lib.df_log_scan.restype = ct.c_int
+    lib.df_log_scan.argtypes = [p, u64, u64, p, p, u64, ct.c_char_p, p, u32,
+                                u32, p, u64]
+    lib.df_log_select.restype = ct.c_int
+    lib.df_log_select.argtypes = [p, p, p, p, u64, u32, i64, i64, u32, u64,
+                                  p, u32, u32, p, p, u64, u32, u64]
 
 
 def gpu() -> ct.CDLL:

@@ -32,7 +32,8 @@ class DeepflowServer:
                  platform_cfg: Optional[SpanGenConfig] = None,
                  native_pump: bool = False,
                  pump_port: int = 0,
-                 gpu_profiles: bool = False):
+                 gpu_profiles: bool = False,
+                 gpu_logs: bool = False):
         self.device = device
         self.kg = KnowledgeGraphTable(device=device)
         if platform_cfg is not None:
@@ -113,7 +114,12 @@ class DeepflowServer:
         from .ingest.event_pipeline import EventPipeline
         from .ingest.applog_pipeline import AppLogPipeline
         self.events = EventPipeline()
-        self.applogs = AppLogPipeline()
+        # gpu_logs: keep application logs in HBM and search them with
+        # HIP kernels (store/log_store.py); off by default
+        if gpu_logs and not str(device).startswith("cpu"):
+            self.applogs = AppLogPipeline(device=device)
+        else:
+            self.applogs = AppLogPipeline()
         self.receiver.register(framing.MSG_PROC_EVENT,
                                lambda hdr, payload:
                                self.events.ingest_proc_events(
@@ -161,6 +167,8 @@ class DeepflowServer:
         from .export.prom_exporter import PromExporter
         self.prom_exporter = PromExporter(self.l7, self.l4)
         self.prom_exporter.register(self.app)
+        from .ingest.applog_pipeline import LogApp
+        LogApp(self.applogs).register(self.app)
         from .query.mcp import McpServer
         self.mcp = McpServer(self.engine, self.profiles)
         self.mcp.register(self.app)

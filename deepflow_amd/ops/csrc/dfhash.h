@@ -1,6 +1,6 @@
 // Device hash helpers shared by the HIP translation units of libdfgpu.so
-// (dfgpu.hip, dfprofile.hip, dftrace.hip, dflog.hip). Internal linkage: each unit gets
-// its own copy.
+// (dfgpu.hip, dfprofile.hip, dftrace.hip, dflog.hip, dfflow.hip). Internal
+// linkage: each unit gets its own copy.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

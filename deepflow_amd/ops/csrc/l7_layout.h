@@ -148,6 +148,8 @@ enum {
 #define L7_POOL_TRACE_ID 2
 #define L7_POOL_SPAN_ID 3
 #define L7_POOL_PARENT_SPAN_ID 4
+#define L7_POOL_X_REQUEST_ID_0 5
+#define L7_POOL_X_REQUEST_ID_1 6
 
 #define DICT_ID_INVALID 0xFFFFFFFFu
 #define STR_REF_PACK(off, len) \

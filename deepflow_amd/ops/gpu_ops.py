@@ -338,6 +338,56 @@ def trace_fold(ws) -> None:
 
 
 # ----------------------------------------------------------------------
+# K12: flow groups (dfflow.hip). `ws` is a query.flowgroups._FlowWorkspace
+# (owns every tensor named here; ws.flat_ptrs is a host u64 array of the
+# flat-column pointers in FlowFlat order).
+# ----------------------------------------------------------------------
+
+def flow_extract(seg, base_row: int, time_start: int, time_end: int,
+                 ws) -> None:
+    lib = native.gpu()
+    native.check(lib.df_flow_extract(
+        seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr(),
+        seg.str_rowref.data_ptr(), seg.str_lens.data_ptr(),
+        seg.pool.data_ptr(), seg.capacity, seg.n_rows, base_row,
+        time_start, time_end, ws.flat_ptrs.ctypes.data,
+        ws.idx_keys.data_ptr(), ws.idx_rows.data_ptr(),
+        ws.drops.data_ptr(), ws.idx_cap, _stream()), "df_flow_extract")
+
+
+def flow_index(ws) -> None:
+    """Index inserts from flat columns already in `ws` (what flow_extract
+    does per segment row); for callers that filled the columns themselves."""
+    lib = native.gpu()
+    native.check(lib.df_flow_index(
+        ws.flat_ptrs.ctypes.data, ws.idx_keys.data_ptr(),
+        ws.idx_rows.data_ptr(), ws.drops.data_ptr(), ws.idx_cap, ws.n,
+        _stream()), "df_flow_index")
+
+
+def flow_union(ws) -> None:
+    lib = native.gpu()
+    native.check(lib.df_flow_union(
+        ws.flat_ptrs.ctypes.data, ws.idx_keys.data_ptr(),
+        ws.idx_rows.data_ptr(), ws.idx_cap, ws.n, ws.label.data_ptr(),
+        ws.via.data_ptr(), _stream()), "df_flow_union")
+
+
+def flow_flatten(ws) -> None:
+    lib = native.gpu()
+    native.check(lib.df_flow_flatten(
+        ws.label.data_ptr(), ws.n, ws.group.data_ptr(), _stream()),
+        "df_flow_flatten")
+
+
+def flow_fold(ws) -> None:
+    lib = native.gpu()
+    native.check(lib.df_flow_fold(
+        ws.flat_ptrs.ctypes.data, ws.group.data_ptr(), ws.via.data_ptr(),
+        ws.n, ws.gvals.data_ptr(), _stream()), "df_flow_fold")
+
+
+# ----------------------------------------------------------------------
 # K11: application-log store + substring search (dflog.hip). `st` is a
 # store.log_store.GpuLogStore (owns every tensor named here).
 # ----------------------------------------------------------------------

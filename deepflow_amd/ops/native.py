@@ -178,6 +178,21 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_trace_fold.restype = ct.c_int
     lib.df_trace_fold.argtypes = [p, p, p, p, u32, p, p, u32, p, p, u32,
                                   p, u64]
+    # K12 flow groups: hash join + union-find (dfflow.hip)
+    for getter in ("df_flow_gv_n", "df_flow_rel_n", "df_flow_keys_per_row"):
+        getattr(lib, getter).restype = u32
+        getattr(lib, getter).argtypes = []
+    lib.df_flow_extract.restype = ct.c_int
+    lib.df_flow_extract.argtypes = [p, p, p, p, p, p, u64, u32, u32, u64,
+                                    u64, p, p, p, p, u32, u64]
+    lib.df_flow_index.restype = ct.c_int
+    lib.df_flow_index.argtypes = [p, p, p, p, u32, u32, u64]
+    lib.df_flow_union.restype = ct.c_int
+    lib.df_flow_union.argtypes = [p, p, p, u32, u32, p, p, u64]
+    lib.df_flow_flatten.restype = ct.c_int
+    lib.df_flow_flatten.argtypes = [p, u32, p, u64]
+    lib.df_flow_fold.restype = ct.c_int
+    lib.df_flow_fold.argtypes = [p, p, p, u32, p, u64]
     # K11 application-log store / substring search (dflog.hip)
     lib.df_log_tile_bytes.restype = u32
     lib.df_log_tile_bytes.argtypes = []

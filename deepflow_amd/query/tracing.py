@@ -125,12 +125,60 @@ class DistributedTracer:
         return {"traces": tm["trace_count"], "spans": tm["span_count"],
                 "drops": tm["drops"], "rows": len(self.tree_rows)}
 
+    # ----------------------------------------------------- flow groups (K12)
+    def flow_groups(self, time_start: Optional[int] = None,
+                    time_end: Optional[int] = None,
+                    min_spans: int = 2) -> Dict:
+        """Summaries of the groups that the spans in [time_start, time_end]
+        form through shared trace ids, syscall trace ids, tcp sequence
+        pairs and x-request-ids, spans without a trace id included; see
+        query/flowgroups.py."""
+        from .flowgroups import FlowGrouper
+        return FlowGrouper(self.engine).flow_groups(time_start, time_end,
+                                                    min_spans)
+
+    def flow_trace(self, time_start: Optional[int] = None,
+                   time_end: Optional[int] = None, *,
+                   trace_id: Optional[str] = None,
+                   syscall_trace_id: Optional[int] = None,
+                   x_request_id: Optional[str] = None,
+                   limit: int = 10000) -> Dict:
+        """The spans of the flow group that one id belongs to, in row
+        order. Exactly one of the three ids must be given."""
+        from .flowgroups import FlowGrouper
+        return FlowGrouper(self.engine).flow_trace(
+            time_start, time_end, trace_id=trace_id,
+            syscall_trace_id=syscall_trace_id, x_request_id=x_request_id,
+            limit=limit)
+
     def register(self, app) -> None:
         # fixed paths first: the parameterised route below would swallow them
         @app.get("/v1/tracing/map")
         def tracing_map(time_start: Optional[int] = None,
                         time_end: Optional[int] = None):
             return self.trace_map(time_start, time_end)
+
+        @app.get("/v1/tracing/groups")
+        def tracing_groups(time_start: Optional[int] = None,
+                           time_end: Optional[int] = None,
+                           min_spans: int = 2):
+            return self.flow_groups(time_start, time_end, min_spans)
+
+        @app.get("/v1/tracing/flow")
+        def tracing_flow(time_start: Optional[int] = None,
+                         time_end: Optional[int] = None,
+                         trace_id: Optional[str] = None,
+                         syscall_trace_id: Optional[int] = None,
+                         x_request_id: Optional[str] = None,
+                         limit: int = 10000):
+            try:
+                return self.flow_trace(
+                    time_start, time_end, trace_id=trace_id,
+                    syscall_trace_id=syscall_trace_id,
+                    x_request_id=x_request_id, limit=limit)
+            except ValueError as e:
+                from fastapi import HTTPException
+                raise HTTPException(status_code=400, detail=str(e))
 
         @app.post("/v1/tracing/trees/build")
         def tracing_build(time_start: Optional[int] = None,

@@ -1383,7 +1383,12 @@ DEV bool eval_terms(const SegView& s, uint64_t row, const QuerySpec& q) {
 
 // group table: gkeys u64 hash (claim word), graw [cap, QMAX_KEYS] raw key
 // values, gvals [cap, QMAX_AGGS] u64 accumulators (min encoded as ~v).
-// group claim: load-first probe, CAS on empty (shared by both agg paths)
+// group claim: load-first probe, CAS on empty (shared by both agg paths).
+// A full table (every slot probed, none free or matching) yields
+// GROUP_FULL: the caller counts the row as overflow instead of merging it
+// into another group; the host reruns with a larger table.
+constexpr uint32_t GROUP_FULL = 0xFFFFFFFFu;
+
 DEV uint32_t group_claim(uint64_t h, const uint64_t* kraw, uint32_t n_keys,
                          uint64_t* gkeys, uint64_t* graw,
                          uint32_t cap_mask) {
@@ -1403,20 +1408,31 @@ DEV uint32_t group_claim(uint64_t h, const uint64_t* kraw, uint32_t n_keys,
         }
         slot = (slot + 1) & cap_mask;
     }
-    return 0;
+    return GROUP_FULL;
 }
 
 constexpr uint32_t QAGG_NSLOT = 512;
+// "no COUNT aggregate in the spec" marker for agg_count_slot()
+constexpr uint32_t NO_COUNT_AGG = 0xFFFFFFFFu;
+
+// A COUNT accumulator already is the per-slot row tally the overflow
+// report needs; only specs without one pay for the separate lrows add.
+DEV uint32_t agg_count_slot(const QuerySpec& q) {
+    for (uint32_t a = 0; a < q.n_aggs; a++)
+        if (q.aggs[a].op == AGGOP_COUNT) return a;
+    return NO_COUNT_AGG;
+}
 
 // One row's LDS-table aggregation (shared by the direct and the
 // partitioned kernels): probe/claim the block-local table, accumulate;
 // on LDS saturation fall through to the global table directly.
 DEV void agg_vals_lds(const QuerySpec& q, uint64_t h,
                       const uint64_t* kraw, const uint64_t* varr,
-                      uint64_t* lkey, uint32_t* lgslot,
+                      uint64_t* lkey, uint32_t* lgslot, uint32_t* lrows,
                       unsigned long long (*lagg)[QMAX_AGGS],
                       uint64_t* gkeys, uint64_t* graw,
-                      unsigned long long* gvals, uint32_t cap_mask) {
+                      unsigned long long* gvals, uint32_t cap_mask,
+                      uint32_t cnt_a, uint32_t* overflow) {
     uint32_t slot = (uint32_t)h & (QAGG_NSLOT - 1);
     uint32_t gslot = 0xFFFFFFFFu;
     for (uint32_t probe = 0; probe < 16; probe++) {
@@ -1444,6 +1460,7 @@ DEV void agg_vals_lds(const QuerySpec& q, uint64_t h,
     // forces FLAT atomics on the LDS path (the compiler can no longer
     // prove addrspace(3)) — measured 2.7x slower on the direct kernel
     if (gslot != 0xFFFFFFFFu) {
+        if (cnt_a == NO_COUNT_AGG) atomicAdd(&lrows[gslot], 1u);
         for (uint32_t a = 0; a < q.n_aggs; a++) {
             uint32_t op = q.aggs[a].op;
             if (op == AGGOP_COUNT || op == AGGOP_SUM)
@@ -1455,6 +1472,10 @@ DEV void agg_vals_lds(const QuerySpec& q, uint64_t h,
         }
     } else {  // LDS table saturated for this key: go global directly
         uint32_t g = group_claim(h, kraw, q.n_keys, gkeys, graw, cap_mask);
+        if (g == GROUP_FULL) {
+            atomicAdd(overflow, 1u);
+            return;
+        }
         unsigned long long* acc = &gvals[(uint64_t)g * QMAX_AGGS];
         for (uint32_t a = 0; a < q.n_aggs; a++) {
             uint32_t op = q.aggs[a].op;
@@ -1469,10 +1490,11 @@ DEV void agg_vals_lds(const QuerySpec& q, uint64_t h,
 }
 
 DEV void agg_row_lds(const SegView& s, const QuerySpec& q, uint64_t row,
-                     uint64_t* lkey, uint32_t* lgslot,
+                     uint64_t* lkey, uint32_t* lgslot, uint32_t* lrows,
                      unsigned long long (*lagg)[QMAX_AGGS],
                      uint64_t* gkeys, uint64_t* graw,
-                     unsigned long long* gvals, uint32_t cap_mask) {
+                     unsigned long long* gvals, uint32_t cap_mask,
+                     uint32_t cnt_a, uint32_t* overflow) {
     uint64_t kraw[QMAX_KEYS];
     uint64_t h = 0x243F6A8885A308D3ull;
     for (uint32_t k = 0; k < q.n_keys; k++) {
@@ -1486,25 +1508,34 @@ DEV void agg_row_lds(const SegView& s, const QuerySpec& q, uint64_t row,
         varr[a] = q.aggs[a].op == AGGOP_COUNT ? 1
             : src_value(s, row, q.aggs[a].family, q.aggs[a].idx, 0,
                         q.time_base_s);
-    agg_vals_lds(q, h, kraw, varr, lkey, lgslot, lagg, gkeys, graw,
-                 gvals, cap_mask);
+    agg_vals_lds(q, h, kraw, varr, lkey, lgslot, lrows, lagg, gkeys, graw,
+                 gvals, cap_mask, cnt_a, overflow);
 }
 
-DEV void agg_lds_init(const QuerySpec& q, uint64_t* lkey,
+DEV void agg_lds_init(const QuerySpec& q, uint64_t* lkey, uint32_t* lrows,
                       unsigned long long (*lagg)[QMAX_AGGS]) {
     for (uint32_t sl = threadIdx.x; sl < QAGG_NSLOT; sl += blockDim.x) {
         lkey[sl] = EMPTY_KEY;
+        lrows[sl] = 0;
         for (uint32_t a = 0; a < q.n_aggs; a++)
             lagg[sl][a] = q.aggs[a].op == AGGOP_MIN ? ~0ull : 0ull;
     }
 }
 
 DEV void agg_lds_flush(const QuerySpec& q, const uint64_t* lkey,
-                       const uint32_t* lgslot,
+                       const uint32_t* lgslot, const uint32_t* lrows,
                        unsigned long long (*lagg)[QMAX_AGGS],
-                       unsigned long long* gvals) {
+                       unsigned long long* gvals, uint32_t cnt_a,
+                       uint32_t* overflow) {
     for (uint32_t sl = threadIdx.x; sl < QAGG_NSLOT; sl += blockDim.x) {
         if (lkey[sl] == EMPTY_KEY) continue;
+        if (lgslot[sl] == GROUP_FULL) {
+            // the group never got a global slot: report its rows
+            uint32_t rows = cnt_a == NO_COUNT_AGG ? lrows[sl]
+                                                  : (uint32_t)lagg[sl][cnt_a];
+            atomicAdd(overflow, rows);
+            continue;
+        }
         unsigned long long* acc = &gvals[(uint64_t)lgslot[sl] * QMAX_AGGS];
         for (uint32_t a = 0; a < q.n_aggs; a++) {
             uint32_t op = q.aggs[a].op;
@@ -1524,10 +1555,11 @@ __global__ void k_query_agg(SegView s, QuerySpec q, uint32_t n, uint64_t base_ro
                             uint64_t* __restrict__ gkeys,
                             uint64_t* __restrict__ graw,
                             unsigned long long* __restrict__ gvals,
-                            uint32_t cap_mask) {
+                            uint32_t cap_mask,
+                            uint32_t* __restrict__ overflow) {
     // Grid-strided scan with an LDS-resident group table: each workgroup
-    // aggregates its stripe into shared memory (~37 KB of the 160 KB/CU
-    // LDS: 512 slots x (key + global-slot + 8 accumulators)) and flushes
+    // aggregates its stripe into shared memory (~40 KB of the 160 KB/CU
+    // LDS: 512 slots x (key + global-slot + row tally + 8 accumulators)) and flushes
     // once at the end — global atomics drop from per-row to
     // per-(block x live slot). Groups are identified by the 64-bit mixed
     // key hash (same convention as the global table); the LDS claimant
@@ -1536,18 +1568,20 @@ __global__ void k_query_agg(SegView s, QuerySpec q, uint32_t n, uint64_t base_ro
     // cardinality) fall back to per-lane global accumulation.
     __shared__ uint64_t lkey[QAGG_NSLOT];
     __shared__ uint32_t lgslot[QAGG_NSLOT];
+    __shared__ uint32_t lrows[QAGG_NSLOT];
     __shared__ unsigned long long lagg[QAGG_NSLOT][QMAX_AGGS];
-    agg_lds_init(q, lkey, lagg);
+    const uint32_t cnt_a = agg_count_slot(q);
+    agg_lds_init(q, lkey, lrows, lagg);
     __syncthreads();
     for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
          i < n; i += (uint64_t)gridDim.x * blockDim.x) {
         uint64_t row = base_row + i;
         if (!eval_terms(s, row, q)) continue;
-        agg_row_lds(s, q, row, lkey, lgslot, lagg, gkeys, graw, gvals,
-                    cap_mask);
+        agg_row_lds(s, q, row, lkey, lgslot, lrows, lagg, gkeys, graw,
+                    gvals, cap_mask, cnt_a, overflow);
     }
     __syncthreads();
-    agg_lds_flush(q, lkey, lgslot, lagg, gvals);
+    agg_lds_flush(q, lkey, lgslot, lrows, lagg, gvals, cnt_a, overflow);
 }
 
 // ---- radix-partitioned group-by (high cardinality) ----
@@ -1679,11 +1713,14 @@ __global__ void k_qpart_agg(QuerySpec q,
                             uint64_t* __restrict__ graw,
                             unsigned long long* __restrict__ gvals,
                             uint32_t cap_mask,
-                            uint32_t blocks_per_bucket) {
+                            uint32_t blocks_per_bucket,
+                            uint32_t* __restrict__ overflow) {
     __shared__ uint64_t lkey[QAGG_NSLOT];
     __shared__ uint32_t lgslot[QAGG_NSLOT];
+    __shared__ uint32_t lrows[QAGG_NSLOT];
     __shared__ unsigned long long lagg[QAGG_NSLOT][QMAX_AGGS];
-    agg_lds_init(q, lkey, lagg);
+    const uint32_t cnt_a = agg_count_slot(q);
+    agg_lds_init(q, lkey, lrows, lagg);
     __syncthreads();
     uint32_t w = q.n_keys + q.n_aggs;
     uint32_t bucket = blockIdx.x / blocks_per_bucket;
@@ -1698,11 +1735,11 @@ __global__ void k_qpart_agg(QuerySpec q,
         for (uint32_t k = 0; k < q.n_keys; k++)
             h = mix64(h ^ row[k] ^ ((uint64_t)k << 56));
         if (h == EMPTY_KEY) h = 1;
-        agg_vals_lds(q, h, row, row + q.n_keys, lkey, lgslot, lagg,
-                     gkeys, graw, gvals, cap_mask);
+        agg_vals_lds(q, h, row, row + q.n_keys, lkey, lgslot, lrows, lagg,
+                     gkeys, graw, gvals, cap_mask, cnt_a, overflow);
     }
     __syncthreads();
-    agg_lds_flush(q, lkey, lgslot, lagg, gvals);
+    agg_lds_flush(q, lkey, lgslot, lrows, lagg, gvals, cnt_a, overflow);
 }
 
 // non-aggregated SELECT: emit matching row ids (bounded)
@@ -1971,6 +2008,7 @@ int df_query_agg(const void* u64c, const void* u32c, const void* u8c,
                  const void* spec,  // QuerySpec, host-built bytes
                  uint32_t n, uint64_t base_row,
                  void* gkeys, void* graw, void* gvals, uint32_t cap,
+                 void* overflow,  // u32: rows whose group found no slot
                  uint64_t stream) {
     SegView s{(const uint64_t*)u64c, (const uint32_t*)u32c, (const uint8_t*)u8c,
               (const uint32_t*)didc,
@@ -1989,7 +2027,8 @@ int df_query_agg(const void* u64c, const void* u32c, const void* u8c,
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(k_query_agg, dim3(blocks), dim3(BLOCK), 0, STREAM(stream),
                        s, q, n, base_row, (uint64_t*)gkeys, (uint64_t*)graw,
-                       (unsigned long long*)gvals, cap - 1);
+                       (unsigned long long*)gvals, cap - 1,
+                       (uint32_t*)overflow);
     return (int)hipGetLastError();
 }
 
@@ -2004,6 +2043,7 @@ int df_qpart_agg(const void* u64c, const void* u32c, const void* u8c,
                  const void* spec, uint32_t n, uint64_t base_row,
                  void* counts, void* cursors, void* row_scratch,
                  void* gkeys, void* graw, void* gvals, uint32_t cap,
+                 void* overflow,  // u32: rows whose group found no slot
                  uint64_t stream) {
     // Three-pass radix-partitioned aggregation. counts/cursors are
     // QPART_NB u32 device buffers; the caller pre-fills cursors with the
@@ -2040,7 +2080,8 @@ int df_qpart_agg(const void* u64c, const void* u32c, const void* u8c,
                        STREAM(stream), q, (const uint64_t*)row_scratch,
                        (const uint32_t*)counts, (const uint32_t*)cursors,
                        (uint64_t*)gkeys, (uint64_t*)graw,
-                       (unsigned long long*)gvals, cap - 1, BPB);
+                       (unsigned long long*)gvals, cap - 1, BPB,
+                       (uint32_t*)overflow);
     return (int)hipGetLastError();
 }
 

@@ -176,7 +176,12 @@ def _opt_ptr(seg, attr: str) -> int:
 
 def query_agg(seg, spec_bytes: bytes, base_row: int, n: int,
               gkeys: torch.Tensor, graw: torch.Tensor,
-              gvals: torch.Tensor, kg=None) -> None:
+              gvals: torch.Tensor, kg=None, *,
+              overflow: torch.Tensor) -> None:
+    """overflow: u32[1] device counter (caller zeroes it): rows whose group
+    found no free slot in the group table. They are left out of every
+    reported group, so a non-zero count means 'rerun with a larger
+    table'."""
     import ctypes
     lib = native.gpu()
     buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
@@ -189,18 +194,20 @@ def query_agg(seg, spec_bytes: bytes, base_row: int, n: int,
         seg.pool.data_ptr(), seg.capacity, seg.n_rows,
         ctypes.addressof(buf), n, base_row,
         gkeys.data_ptr(), graw.data_ptr(), gvals.data_ptr(), gkeys.numel(),
-        _stream()), "df_query_agg")
+        overflow.data_ptr(), _stream()), "df_query_agg")
 
 
 def qpart_agg(seg, spec_bytes: bytes, base_row: int, n: int,
               counts: torch.Tensor, cursors: torch.Tensor,
               row_scratch: torch.Tensor,
               gkeys: torch.Tensor, graw: torch.Tensor,
-              gvals: torch.Tensor, kg=None) -> None:
+              gvals: torch.Tensor, kg=None, *,
+              overflow: torch.Tensor) -> None:
     """Radix-partitioned group-by (high key cardinality): bucket rows by
     8 hash bits, aggregate one bucket per workgroup set — each block's
     LDS table then holds every key it sees (no per-row global atomics).
-    counts/cursors: u32[256] (counts zeroed); row_scratch:\n    u64[n * (n_keys+n_aggs)] payload staging."""
+    counts/cursors: u32[256] (counts zeroed); row_scratch:\n    u64[n * (n_keys+n_aggs)] payload staging; overflow: as in
+    query_agg."""
     import ctypes
     lib = native.gpu()
     buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
@@ -214,7 +221,7 @@ def qpart_agg(seg, spec_bytes: bytes, base_row: int, n: int,
         ctypes.addressof(buf), n, base_row,
         counts.data_ptr(), cursors.data_ptr(), row_scratch.data_ptr(),
         gkeys.data_ptr(), graw.data_ptr(), gvals.data_ptr(),
-        gkeys.numel(), _stream()), "df_qpart_agg")
+        gkeys.numel(), overflow.data_ptr(), _stream()), "df_qpart_agg")
 
 
 def _kg_args(kg):

@@ -21,7 +21,8 @@ from .spec import (Plan, SRC_U64, SRC_U32, SRC_U8, SRC_DID, SRC_KG,
                    QMAX_KEYS, QMAX_AGGS)
 
 U64MAX = (1 << 64) - 1
-GROUP_CAP = 1 << 20
+GROUP_CAP = 1 << 20       # first-try group table slots (power of two)
+GROUP_CAP_MAX = 1 << 24   # growth limit when the kernels report overflow
 
 
 def _src_np(seg, family: int, idx: int, bucket: int, time_base_s: int,
@@ -192,7 +193,7 @@ def execute_agg_cpu(plan: Plan, segments, kg=None) -> List[Dict]:
             for ai, a in enumerate(plan.aggs):
                 v = int(aggvals[ai][r])
                 if a.op in (AGGOP_COUNT, AGGOP_SUM):
-                    acc[ai] += v
+                    acc[ai] = (acc[ai] + v) & U64MAX  # u64 accumulator
                 elif a.op == AGGOP_MIN:
                     acc[ai] = min(acc[ai], v)
                 else:
@@ -223,33 +224,58 @@ def _qpart_scratch(dev, need_elems: int):
     return sc
 
 
-def execute_agg_gpu(plan: Plan, segments, device="cuda", kg=None) -> List[Dict]:
+def _agg_pass_gpu(plan: Plan, segments, dev, kg, cap: int, use_qpart: bool):
+    """One aggregation pass over all segments into a `cap`-slot group
+    table. -> (gkeys, graw, gvals, rows that found no slot)."""
     from ..ops import gpu_ops
-    dev = torch.device(device)
-    gkeys = torch.zeros(GROUP_CAP, dtype=torch.int64, device=dev)
-    graw = torch.zeros((GROUP_CAP, QMAX_KEYS), dtype=torch.int64, device=dev)
-    gvals = torch.zeros((GROUP_CAP, QMAX_AGGS), dtype=torch.int64, device=dev)
+    # the overflow counter rides behind the key words: one memset fewer
+    # per query than a tensor of its own
+    kbuf = torch.zeros(cap + 1, dtype=torch.int64, device=dev)
+    gkeys, overflow = kbuf[:cap], kbuf[cap:].view(torch.int32)
+    graw = torch.zeros((cap, QMAX_KEYS), dtype=torch.int64, device=dev)
+    gvals = torch.zeros((cap, QMAX_AGGS), dtype=torch.int64, device=dev)
     for ai, a in enumerate(plan.aggs):
         if a.op == AGGOP_MIN:
             gvals[:, ai] = -1  # 0xFFFF.. as int64
     spec = plan.to_bytes()
-    key_sig = tuple((k.family, k.idx, k.bucket) for k in plan.keys)
-    known_card = _CARDINALITY_CACHE.get(key_sig, 0)
     for seg in segments:
         if seg.n_rows == 0:
             continue
-        if known_card >= _QPART_MIN_GROUPS and \
-                seg.n_rows >= _QPART_MIN_ROWS and plan.keys:
+        if use_qpart and seg.n_rows >= _QPART_MIN_ROWS:
             w = len(plan.keys) + len(plan.aggs)
             scratch = _qpart_scratch(dev, seg.n_rows * w)
             scratch[0].zero_()
             gpu_ops.qpart_agg(seg, spec, 0, seg.n_rows, scratch[0],
                               scratch[1], scratch[2], gkeys, graw, gvals,
-                              kg=kg)
+                              kg=kg, overflow=overflow)
         else:
             gpu_ops.query_agg(seg, spec, 0, seg.n_rows, gkeys, graw,
-                              gvals, kg=kg)
-    torch.cuda.synchronize()
+                              gvals, kg=kg, overflow=overflow)
+    # reading the counter back is the wait for the launches above (all on
+    # the current stream); a separate synchronize would be a second wait
+    lost = int(overflow[0].item()) & 0xFFFFFFFF
+    return gkeys, graw, gvals, lost
+
+
+def execute_agg_gpu(plan: Plan, segments, device="cuda", kg=None) -> List[Dict]:
+    dev = torch.device(device)
+    key_sig = tuple((k.family, k.idx, k.bucket) for k in plan.keys)
+    known_card = _CARDINALITY_CACHE.get(key_sig, 0)
+    use_qpart = known_card >= _QPART_MIN_GROUPS and bool(plan.keys)
+    cap = GROUP_CAP
+    while True:
+        gkeys, graw, gvals, lost = _agg_pass_gpu(plan, segments, dev, kg,
+                                                 cap, use_qpart)
+        if not lost:
+            break
+        # the kernels leave rows of groups that found no slot out of the
+        # result and count them: rerun with a larger table
+        if cap >= GROUP_CAP_MAX:
+            raise RuntimeError(
+                f"GROUP BY produces more than {GROUP_CAP_MAX} groups "
+                f"(group table limit); narrow the filter or the key set")
+        del gkeys, graw, gvals
+        cap = min(cap * 4, GROUP_CAP_MAX)
     mask = gkeys != 0
     raw = graw[mask].cpu().numpy().view(np.uint64)
     vals = gvals[mask].cpu().numpy().view(np.uint64)

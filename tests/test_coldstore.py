@@ -184,3 +184,34 @@ def test_l4_cold_tier():
     assert l4.segments.demote_oldest()
     got = eng.query(q)
     assert want == got
+
+
+def pack_bits_py(deltas, bits):
+    """Bit-string packer: value i owns stream bits [i*bits, (i+1)*bits),
+    least significant first; stream bit j is bit j%32 of word j//32."""
+    s = "".join(format(d, f"0{bits}b")[::-1] for d in deltas)
+    s += "0" * (-len(s) % 32)
+    return [int(s[i:i + 32][::-1], 2) for i in range(0, len(s), 32)]
+
+
+def _as_i32(vals):
+    return torch.tensor([v - (1 << 32) if v >= (1 << 31) else v
+                         for v in vals], dtype=torch.int32)
+
+
+@pytest.mark.parametrize("base", [0, 12345, 2**31 + 7])
+def test_cpu_packer_matches_bit_string_packer(base):
+    import random
+    rng = random.Random(base)
+    for bits in range(1, 33):
+        top = (1 << bits) - 1
+        for n in (1, 31, 32, 33, 4097):
+            deltas = [rng.randint(0, top) for _ in range(n)]
+            deltas[0] = deltas[n // 2] = top
+            want = _as_i32(pack_bits_py(deltas, bits))
+            got = C._pack_words_cpu(torch.tensor(deltas, dtype=torch.int64),
+                                    bits)
+            assert torch.equal(got, want), (bits, n)
+            v32 = _as_i32([(base + d) & 0xFFFFFFFF for d in deltas])
+            assert torch.equal(C.pack_stream(v32, base, bits), want)
+            assert torch.equal(C.unpack_stream(got, n, base, bits), v32)

@@ -52,3 +52,68 @@ def test_query_over_cold_gpu():
     assert hot_bytes / cold_bytes > 1.5
     got = [eng.query(q) for q in queries]
     assert want == got
+
+
+def pack_bits_py(deltas, bits):
+    """Bit-string packer: value i owns stream bits [i*bits, (i+1)*bits),
+    least significant first; stream bit j is bit j%32 of word j//32."""
+    s = "".join(format(d, f"0{bits}b")[::-1] for d in deltas)
+    s += "0" * (-len(s) % 32)
+    return [int(s[i:i + 32][::-1], 2) for i in range(0, len(s), 32)]
+
+
+def _as_i32(vals):
+    return torch.tensor([v - (1 << 32) if v >= (1 << 31) else v
+                         for v in vals], dtype=torch.int32)
+
+
+@pytest.mark.parametrize("base", [0, 12345, 2**31 + 7])
+def test_pack_kernels_every_width(base):
+    """Every width 1..32 at sizes around the 32-value period and past one
+    block, values on both sides of the int32 sign bit."""
+    import random
+    rng = random.Random(base)
+    for bits in range(1, 33):
+        top = (1 << bits) - 1
+        for n in (1, 31, 32, 33, 4097):
+            deltas = [rng.randint(0, top) for _ in range(n)]
+            deltas[0] = top
+            deltas[-1] = top if n < 32 else 0
+            deltas[n // 2] = top
+            v32 = _as_i32([(base + d) & 0xFFFFFFFF for d in deltas])
+            want = _as_i32(pack_bits_py(deltas, bits))
+            got = C.pack_stream(v32.cuda(), base, bits)
+            back = C.unpack_stream(got, n, base, bits)
+            torch.cuda.synchronize()
+            assert torch.equal(got.cpu(), want), (bits, n)
+            assert torch.equal(back.cpu(), v32), (bits, n)
+
+
+def test_constant_columns_pack_to_nothing():
+    """A constant column (and an empty one) is (base, bits=0, no payload):
+    neither kernel is launched for it."""
+    n = 300
+    m32 = torch.zeros((4, 512), dtype=torch.int32)
+    m32[0, :n] = 7
+    m32[1, :n] = -1                          # stored as 0xFFFFFFFF
+    # columns are stored unsigned: 2^31-150 .. 2^31+149 is one 9-bit range
+    m32[2, :n] = _as_i32([2**31 - 150 + i for i in range(n)])
+    m32[3, :n] = -(2**31)
+    m64 = torch.zeros((2, 512), dtype=torch.int64)
+    m64[0, :n] = 2**40 + 3
+    m64[1, :n] = 2**40 + torch.arange(n)
+    for mat, const_rows in ((m32, {0, 1, 3}), (m64, {0})):
+        dmat = mat.cuda()
+        for rows in (n, 0):
+            cols = C._compress_i32_matrix(dmat, rows)
+            for c, pc in enumerate(cols):
+                if rows == 0 or c in const_rows:
+                    assert (pc.bits, pc.data, pc.raw) == (0, None, None)
+                    assert pc.nbytes() == 0
+                else:
+                    assert pc.bits == 9 and pc.data.numel() == (n * 9 + 31) // 32
+            out = torch.full_like(dmat, 99)
+            C._restore_i32_matrix(cols, out, rows)
+            torch.cuda.synchronize()
+            assert torch.equal(out[:, :rows].cpu(), mat[:, :rows])
+            assert bool((out[:, rows:] == 99).all())

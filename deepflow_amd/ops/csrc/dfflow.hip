@@ -16,15 +16,10 @@
 // k_flow_index is the insert half of k_flow_extract over flat columns that
 // are already on the device (kernel tests; not on the query path).
 //
-// Rules (same as dftrace.hip):
-//  - wave = 64 lanes; blocks are multiples of 64.
-//  - cross-workgroup state is written with device-scope atomics only, and
-//    no kernel reads in the same launch what another workgroup wrote, with
+// Rules: wave = 64 lanes, blocks are multiples of 64; table rules are in
+// dftable.h, segment access in dfseg.h. Particular to this unit:
+//  - no kernel reads in the same launch what another workgroup wrote, with
 //    the one exception below.
-//  - an index slot is claimed with one atomicCAS on its 64-bit key; its row
-//    word is an atomicMin on a host-initialised word.
-//  - probe loops are bounded by the table size; overflow is counted in
-//    `drops`, never waited out. EMPTY_KEY = 0 is reserved.
 //  - an index key is the 64-bit mix of (key space, join key); two different
 //    pairs with one mix would share a slot, the same 64-bit identity K10
 //    already accepts.
@@ -43,19 +38,10 @@
 // Every access to label[] in that kernel is an atomic RMW or a relaxed
 // agent-scope atomic load (served by L2/memory, not by a CU's L1, which no
 // other CU's store refreshes). The later launches read it plainly.
-#include <hip/hip_runtime.h>
-#include "l7_layout.h"
-
-#define DEV __device__ __forceinline__
-#include "dfhash.h"
+#include "dftable.h"
+#include "dfseg.h"
 
 namespace {
-
-constexpr uint64_t EMPTY_KEY = 0ull;
-constexpr uint32_t BLOCK = 256;
-constexpr uint32_t ROW_NONE = 0xFFFFFFFFu;
-// seed of pooled-string filter hashes (dfgpu.hip STR_FILTER_SEED)
-constexpr uint64_t TRACE_STR_SEED = 0x5157A15E5EEDull;
 
 // key spaces (python twin: flowgroups.REL_*); bit r of `via` = space r
 enum { REL_TRACE = 0, REL_SYSCALL, REL_TCP, REL_XREQ, REL_N };
@@ -64,20 +50,6 @@ enum { GV_SPANS = 0, GV_TRACED, GV_ERRORS, GV_START_MIN, GV_END_MAX,
        GV_FIRST_TRACED_ROW, GV_VIA_TRACE, GV_VIA_SYSCALL, GV_VIA_TCP,
        GV_VIA_XREQ, GV_N };
 constexpr uint32_t FLOW_KEYS_PER_ROW = 6;
-
-constexpr uint32_t STATUS_SERVER_ERROR = 3;
-constexpr uint32_t STATUS_CLIENT_ERROR = 4;
-
-struct FlowSeg {
-    const uint64_t* u64c;        // [L7_U64_N, stride]
-    const uint32_t* u32c;        // [L7_U32_N, stride]
-    const uint8_t* u8c;          // [L7_U8_N, stride]
-    const uint64_t* str_rowref;  // [stride] (pool_off<<16 | total_len)
-    const int16_t* str_lens;     // [n_pool_cols, stride]
-    const uint8_t* pool;
-    uint64_t stride;
-    uint32_t n_rows;
-};
 
 // query-scoped flat columns, indexed by global row. Only `part` is written
 // for a row outside the window.
@@ -94,56 +66,19 @@ struct FlowFlat {
     uint8_t* status;    // response_status
 };
 
-// one first-row index for all key spaces
-struct FlowIdx {
-    uint64_t* keys;
-    uint32_t* rows;              // host-initialised to ROW_NONE
-    unsigned long long* drops;
-    uint32_t cap;                // power of two
-};
-
+// one first-row index (FirstRowIdx at base 0) for all key spaces
 DEV uint64_t flow_key(uint32_t rel, uint64_t k) {
     uint64_t h = mix64(mix64(0xF10Full + rel) ^ k);
     return h ? h : 1ull;
 }
 
-// probe-or-insert; plain loads on the hit path (a stale EMPTY is corrected
-// by the CAS). Returns the slot, or ROW_NONE when the table is full.
-DEV uint32_t claim_slot(uint64_t h, uint64_t* tkeys, uint32_t cap_mask) {
-    uint32_t slot = (uint32_t)(mix64(h) & cap_mask);
-    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-        uint64_t cur = tkeys[slot];
-        if (cur == h) return slot;
-        if (cur == EMPTY_KEY) {
-            uint64_t old = atomicCAS((unsigned long long*)&tkeys[slot],
-                                     EMPTY_KEY, h);
-            if (old == EMPTY_KEY || old == h) return slot;
-        }
-        slot = (slot + 1) & cap_mask;
-    }
-    return ROW_NONE;
-}
-
-DEV void idx_insert(const FlowIdx& ix, uint32_t rel, uint64_t k,
+DEV void idx_insert(const FirstRowIdx& ix, uint32_t rel, uint64_t k,
                     uint32_t row) {
-    if (k == 0) return;
-    uint32_t slot = claim_slot(flow_key(rel, k), ix.keys, ix.cap - 1);
-    if (slot == ROW_NONE) atomicAdd(ix.drops, 1ull);
-    else atomicMin(&ix.rows[slot], row);
+    if (k) first_row_insert(ix, 0, flow_key(rel, k), row);
 }
 
-// read-only probe (a later launch than the inserts); ROW_NONE = not there
-DEV uint32_t idx_find(const FlowIdx& ix, uint32_t rel, uint64_t k) {
-    uint64_t h = flow_key(rel, k);
-    uint32_t cap_mask = ix.cap - 1;
-    uint32_t slot = (uint32_t)(mix64(h) & cap_mask);
-    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-        uint64_t cur = ix.keys[slot];
-        if (cur == h) return ix.rows[slot];
-        if (cur == EMPTY_KEY) return ROW_NONE;
-        slot = (slot + 1) & cap_mask;
-    }
-    return ROW_NONE;
+DEV uint32_t idx_find(const FirstRowIdx& ix, uint32_t rel, uint64_t k) {
+    return first_row_find(ix, 0, flow_key(rel, k));
 }
 
 // the (up to) six keys of a row, in a fixed order: trace, syscall request,
@@ -169,42 +104,31 @@ DEV RowKeys load_keys(const FlowFlat& f, uint32_t g) {
     return r;
 }
 
-DEV void insert_keys(const FlowIdx& ix, const RowKeys& r, uint32_t g) {
+DEV void insert_keys(const FirstRowIdx& ix, const RowKeys& r, uint32_t g) {
     for (uint32_t i = 0; i < FLOW_KEYS_PER_ROW; i++)
         idx_insert(ix, key_rel(i), r.k[i], g);
 }
 
-DEV uint64_t pool_hash(const FlowSeg& s, uint64_t row, uint32_t idx) {
-    uint64_t off = STR_REF_OFF(s.str_rowref[row]);
-    for (uint32_t c = 0; c < idx; c++)
-        off += (uint16_t)s.str_lens[(uint64_t)c * s.stride + row];
-    uint32_t len = (uint16_t)s.str_lens[(uint64_t)idx * s.stride + row];
-    return len ? str_hash(s.pool + off, len, TRACE_STR_SEED) : 0;
-}
-
 // one thread per segment row
-__global__ void k_flow_extract(FlowSeg s, uint32_t base_row,
+__global__ void k_flow_extract(SegView s, uint32_t base_row,
                                uint64_t time_start, uint64_t time_end,
-                               FlowFlat f, FlowIdx ix) {
+                               FlowFlat f, FirstRowIdx ix) {
     uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= s.n_rows) return;
+    if (r >= (uint32_t)s.n_rows) return;
     uint32_t g = base_row + r;
     uint64_t start = s.u64c[(uint64_t)L7_U64_START_TIME * s.stride + r];
     bool part = start >= time_start && start <= time_end;
     f.part[g] = part;
     if (!part) return;
     RowKeys k;
-    // the SRC_TRACE128 idx 0 value (dfgpu.hip src_value)
-    uint64_t hi = s.u64c[(uint64_t)L7_U64_TRACE_HI * s.stride + r];
-    uint64_t lo = s.u64c[(uint64_t)L7_U64_TRACE_LO * s.stride + r];
-    k.k[0] = (hi | lo) ? (mix64(hi) ^ lo) : pool_hash(s, r, L7_POOL_TRACE_ID);
+    k.k[0] = seg_trace_key(s, r);
     k.k[1] = s.u64c[(uint64_t)L7_U64_SYSCALL_REQ * s.stride + r];
     k.k[2] = s.u64c[(uint64_t)L7_U64_SYSCALL_RESP * s.stride + r];
     uint32_t req = s.u32c[(uint64_t)L7_U32_REQ_TCP_SEQ * s.stride + r];
     uint32_t resp = s.u32c[(uint64_t)L7_U32_RESP_TCP_SEQ * s.stride + r];
     k.k[3] = req ? ((uint64_t)req | ((uint64_t)resp << 32)) : 0;
-    k.k[4] = pool_hash(s, r, L7_POOL_X_REQUEST_ID_0);
-    k.k[5] = pool_hash(s, r, L7_POOL_X_REQUEST_ID_1);
+    k.k[4] = seg_pool_hash(s, r, L7_POOL_X_REQUEST_ID_0);
+    k.k[5] = seg_pool_hash(s, r, L7_POOL_X_REQUEST_ID_1);
     f.tkey[g] = k.k[0];
     f.sreq[g] = k.k[1];
     f.sresp[g] = k.k[2];
@@ -218,7 +142,7 @@ __global__ void k_flow_extract(FlowSeg s, uint32_t base_row,
 }
 
 // one thread per global row: the index inserts alone, from the flat columns
-__global__ void k_flow_index(FlowFlat f, FlowIdx ix, uint32_t n) {
+__global__ void k_flow_index(FlowFlat f, FirstRowIdx ix, uint32_t n) {
     uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n || !f.part[g]) return;
     insert_keys(ix, load_keys(f, g), g);
@@ -260,7 +184,7 @@ DEV void unite(uint32_t* label, uint32_t a, uint32_t b) {
 }
 
 // one thread per global row. rep < n: only rows below n were inserted.
-__global__ void k_flow_union(FlowFlat f, FlowIdx ix, uint32_t n,
+__global__ void k_flow_union(FlowFlat f, FirstRowIdx ix, uint32_t n,
                              uint32_t* label, uint8_t* __restrict__ via) {
     uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
     if (g >= n || !f.part[g]) return;
@@ -313,10 +237,6 @@ __global__ void k_flow_fold(FlowFlat f, const uint32_t* __restrict__ group,
         if (v & (1u << r)) atomicAdd(&gv[GV_VIA_TRACE + r], 1ull);
 }
 
-inline uint32_t grid_for(uint64_t total) {
-    return (uint32_t)((total + BLOCK - 1) / BLOCK);
-}
-
 inline FlowFlat flat_of(const uint64_t* p) {
     return FlowFlat{(uint8_t*)p[0], (uint64_t*)p[1], (uint64_t*)p[2],
                     (uint64_t*)p[3], (uint64_t*)p[4], (uint64_t*)p[5],
@@ -325,8 +245,6 @@ inline FlowFlat flat_of(const uint64_t* p) {
 }
 
 }  // namespace
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" {
 
@@ -343,12 +261,17 @@ int df_flow_extract(const void* u64c, const void* u32c, const void* u8c,
                     void* idx_rows, void* drops, uint32_t idx_cap,
                     uint64_t stream) {
     if (n_rows == 0) return 0;
-    FlowSeg s{(const uint64_t*)u64c, (const uint32_t*)u32c,
-              (const uint8_t*)u8c, (const uint64_t*)str_rowref,
-              (const int16_t*)str_lens, (const uint8_t*)pool, stride,
-              n_rows};
-    FlowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows,
-               (unsigned long long*)drops, idx_cap};
+    SegView s{};
+    s.u64c = (const uint64_t*)u64c;
+    s.u32c = (const uint32_t*)u32c;
+    s.u8c = (const uint8_t*)u8c;
+    s.str_rowref = (const uint64_t*)str_rowref;
+    s.str_lens = (const int16_t*)str_lens;
+    s.pool = (const uint8_t*)pool;
+    s.stride = stride;
+    s.n_rows = n_rows;
+    FirstRowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows,
+                   (unsigned long long*)drops, idx_cap};
     hipLaunchKernelGGL(k_flow_extract, dim3(grid_for(n_rows)), dim3(BLOCK),
                        0, STREAM(stream), s, base_row, time_start, time_end,
                        flat_of(flat), ix);
@@ -359,8 +282,8 @@ int df_flow_index(const uint64_t* flat, void* idx_keys, void* idx_rows,
                   void* drops, uint32_t idx_cap, uint32_t n,
                   uint64_t stream) {
     if (n == 0) return 0;
-    FlowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows,
-               (unsigned long long*)drops, idx_cap};
+    FirstRowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows,
+                   (unsigned long long*)drops, idx_cap};
     hipLaunchKernelGGL(k_flow_index, dim3(grid_for(n)), dim3(BLOCK), 0,
                        STREAM(stream), flat_of(flat), ix, n);
     return (int)hipGetLastError();
@@ -371,7 +294,8 @@ int df_flow_union(const uint64_t* flat, const void* idx_keys,
                   const void* idx_rows, uint32_t idx_cap, uint32_t n,
                   void* label, void* via, uint64_t stream) {
     if (n == 0) return 0;
-    FlowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows, nullptr, idx_cap};
+    FirstRowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows, nullptr,
+                   idx_cap};
     hipLaunchKernelGGL(k_flow_union, dim3(grid_for(n)), dim3(BLOCK), 0,
                        STREAM(stream), flat_of(flat), ix, n,
                        (uint32_t*)label, (uint8_t*)via);

@@ -14,20 +14,17 @@
 //  - all cross-workgroup state (hash tables, counters) uses device-scope
 //    atomics; no inter-workgroup ordering is assumed (XCD L2s not coherent).
 //  - dictionary/table IDs are SLOT INDICES: a claim is one atomicCAS on the
-//    64-bit key; no ID counter, no spin-waiting on a second word.
+//    64-bit key; no ID counter, no spin-waiting on a second word. The
+//    rules and the one probe-or-insert are in dftable.h; segment access
+//    shared with the other units is in dfseg.h.
 //
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC
 #include <hip/hip_runtime.h>
 #include <rocprim/device/device_radix_sort.hpp>
-#include "l7_layout.h"
-
-#define DEV __device__ __forceinline__
-#include "dfhash.h"  // str_hash, mix64 (shared with dfprofile.hip)
+#include "dftable.h"
+#include "dfseg.h"
 
 namespace {
-
-constexpr uint64_t EMPTY_KEY = 0ull;       // hash tables reserve 0 = empty
-constexpr uint32_t BLOCK = 256;
 
 // Word-buffered byte stream: protobuf parsing is byte-granular and
 // sequential per record; buffering an aligned u64 per 8 bytes turns 8
@@ -927,17 +924,12 @@ __global__ void k_kg_build(const uint64_t* __restrict__ keys,
     if (i >= n) return;
     uint64_t k = keys[i];
     if (k == EMPTY_KEY) return;
-    uint32_t slot = (uint32_t)(mix64(k) & cap_mask);
-    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-        uint64_t old = atomicCAS((unsigned long long*)&tkeys[slot], EMPTY_KEY, k);
-        if (old == EMPTY_KEY || old == k) {
-            // last-writer-wins value update (platform data refresh semantics)
-            for (int j = 0; j < KG_VALS_N; j++)
-                tvals[(uint64_t)slot * KG_VALS_N + j] = vals[(uint64_t)i * KG_VALS_N + j];
-            return;
-        }
-        slot = (slot + 1) & cap_mask;
-    }
+    uint32_t slot = table_claim(tkeys, cap_mask, k,
+                                (uint32_t)(mix64(k) & cap_mask));
+    if (slot == ROW_NONE) return;
+    // last-writer-wins value update (platform data refresh semantics)
+    for (int j = 0; j < KG_VALS_N; j++)
+        tvals[(uint64_t)slot * KG_VALS_N + j] = vals[(uint64_t)i * KG_VALS_N + j];
 }
 
 __global__ void k_kg_probe(const uint32_t* __restrict__ epc0,
@@ -957,17 +949,11 @@ __global__ void k_kg_probe(const uint32_t* __restrict__ epc0,
         uint64_t k = side == 0
             ? (((uint64_t)epc0[i] << 32) | ip0[i])
             : (((uint64_t)epc1[i] << 32) | ip1[i]);
-        uint32_t slot = (uint32_t)(mix64(k) & cap_mask);
-        bool found = false;
-        for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-            uint64_t tk = tkeys[slot];
-            if (tk == k) { found = true; break; }
-            if (tk == EMPTY_KEY) break;
-            slot = (slot + 1) & cap_mask;
-        }
+        uint32_t slot = table_find(tkeys, cap_mask, k,
+                                   (uint32_t)(mix64(k) & cap_mask));
         for (int j = 0; j < KG_VALS_N; j++)
             out[((uint64_t)(side * KG_VALS_N + j)) * stride + row] =
-                found ? tvals[(uint64_t)slot * KG_VALS_N + j] : 0u;
+                slot != ROW_NONE ? tvals[(uint64_t)slot * KG_VALS_N + j] : 0u;
     }
 }
 
@@ -978,33 +964,23 @@ __global__ void k_kg_probe(const uint32_t* __restrict__ epc0,
 // harvest into the id->string dictionary + flow_tag write path.
 // ----------------------------------------------------------------------
 
-// probe-or-insert: plain loads on the hot (hit) path, atomicCAS only on
-// empty slots. Newly claimed slots are emitted for host harvest.
+// probe-or-insert from `h & mask` (dictionary ids are slot indices).
+// Newly claimed slots are emitted for host harvest.
 DEV uint32_t intern_probe(uint64_t h, uint64_t ref, uint8_t domain,
                           uint64_t* tkeys, uint32_t cap_mask,
                           uint64_t* emit, uint32_t* emit_ctr,
                           uint32_t emit_cap) {
-    uint32_t slot = (uint32_t)(h & cap_mask);
-    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-        uint64_t cur = tkeys[slot];
-        if (cur == h) return slot;
-        if (cur == EMPTY_KEY) {
-            uint64_t old = atomicCAS((unsigned long long*)&tkeys[slot],
-                                     EMPTY_KEY, h);
-            if (old == EMPTY_KEY) {
-                uint32_t e = atomicAdd(emit_ctr, 1u);
-                if (e < emit_cap) {
-                    emit[(uint64_t)e * 2] = ((uint64_t)domain << 56) | slot;
-                    emit[(uint64_t)e * 2 + 1] = ref;
-                }
-                return slot;
-            }
-            if (old == h) return slot;
-            // lost the race to a different key: fall through, keep probing
+    bool claimed;
+    uint32_t slot = table_claim(tkeys, cap_mask, h, (uint32_t)(h & cap_mask),
+                                &claimed);
+    if (claimed) {
+        uint32_t e = atomicAdd(emit_ctr, 1u);
+        if (e < emit_cap) {
+            emit[(uint64_t)e * 2] = ((uint64_t)domain << 56) | slot;
+            emit[(uint64_t)e * 2 + 1] = ref;
         }
-        slot = (slot + 1) & cap_mask;
     }
-    return DICT_ID_INVALID;
+    return slot;
 }
 
 // wave-cooperative variant: when every active lane holds the same hash
@@ -1222,8 +1198,6 @@ enum {
     // binary columns, or the pooled-string hash for non-hex fallbacks
     SRC_TRACE128,
 };
-// seed for SRC_STR_HASH terms (host twin: store/dictionary.py STR_FILTER_SEED)
-#define STR_FILTER_SEED 0x5157A15E5EEDull
 // filter ops
 enum { OP_EQ = 0, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_BETWEEN };
 // agg ops
@@ -1249,28 +1223,6 @@ struct QuerySpec {
     uint64_t time_base_s;
 };
 
-struct SegView {
-    const uint64_t* u64c;
-    const uint32_t* u32c;
-    const uint8_t* u8c;
-    const uint32_t* didc;      // [L7_DID_N, stride]
-    // KnowledgeGraph table for query-time join (SmartEncoding: the 24
-    // per-row KG id columns are NOT materialized — they are a pure
-    // function of the row's (epc, ip) key, resolved here by probing the
-    // GPU-resident platform table instead of spending 96 B/span of HBM)
-    const uint64_t* kg_tk;
-    const uint32_t* kg_tv;     // [cap, KG_VALS_N]
-    uint32_t kg_mask;
-    const int32_t* attr_pool;  // variable attr-id pool
-    const uint32_t* attr_start;  // [stride] row block offsets into attr_pool
-    const uint8_t* attr_cnt;   // [stride]
-    const uint64_t* str_rowref;  // [stride] (pool_off<<16 | total_len)
-    const int16_t* str_lens;   // [n_pool_cols, stride]
-    const uint8_t* pool;       // segment string pool
-    uint64_t stride;
-    uint64_t n_rows;
-};
-
 // epc/ip column indices are identical in the L7 and L4 u32 layouts
 // (vtap, ip4_0, ip4_1, epc_0, epc_1 — asserted in the layout headers)
 DEV uint64_t kg_join(const SegView& s, uint64_t row, uint16_t idx) {
@@ -1279,24 +1231,9 @@ DEV uint64_t kg_join(const SegView& s, uint64_t row, uint16_t idx) {
     uint32_t epc = s.u32c[(uint64_t)(3 + side) * s.stride + row];
     uint32_t ip = s.u32c[(uint64_t)(1 + side) * s.stride + row];
     uint64_t k = ((uint64_t)epc << 32) | ip;
-    uint32_t slot = (uint32_t)(mix64(k) & s.kg_mask);
-    for (uint32_t probe = 0; probe <= s.kg_mask; probe++) {
-        uint64_t tk = s.kg_tk[slot];
-        if (tk == k) return s.kg_tv[(uint64_t)slot * KG_VALS_N + j];
-        if (tk == EMPTY_KEY) return 0;
-        slot = (slot + 1) & s.kg_mask;
-    }
-    return 0;
-}
-
-DEV uint64_t pool_str_hash(const SegView& s, uint64_t row, uint16_t idx) {
-    uint64_t rr = s.str_rowref[row];
-    uint64_t off = STR_REF_OFF(rr);
-    for (uint16_t c = 0; c < (uint16_t)idx; c++)
-        off += (uint16_t)s.str_lens[(uint64_t)c * s.stride + row];
-    uint32_t len = (uint16_t)s.str_lens[(uint64_t)idx * s.stride + row];
-    if (len == 0) return 0;
-    return str_hash(s.pool + off, len, STR_FILTER_SEED);
+    uint32_t slot = table_find(s.kg_tk, s.kg_mask, k,
+                               (uint32_t)(mix64(k) & s.kg_mask));
+    return slot == ROW_NONE ? 0 : s.kg_tv[(uint64_t)slot * KG_VALS_N + j];
 }
 
 DEV uint64_t src_value(const SegView& s, uint64_t row, uint8_t family,
@@ -1320,18 +1257,9 @@ DEV uint64_t src_value(const SegView& s, uint64_t row, uint8_t family,
             return bucket ? (rel / bucket) * bucket : rel;
         }
         case SRC_STR_HASH:
-            return pool_str_hash(s, row, idx);
-        case SRC_TRACE128: {
-            if (idx == 0) {
-                uint64_t hi = s.u64c[L7_U64_TRACE_HI * s.stride + row];
-                uint64_t lo = s.u64c[L7_U64_TRACE_LO * s.stride + row];
-                if (hi | lo) return mix64(hi) ^ lo;
-                return pool_str_hash(s, row, L7_POOL_TRACE_ID);
-            }
-            uint64_t sv = s.u64c[L7_U64_SPAN_ID_B * s.stride + row];
-            if (sv) return sv;
-            return pool_str_hash(s, row, L7_POOL_SPAN_ID);
-        }
+            return seg_pool_hash(s, row, idx);
+        case SRC_TRACE128:
+            return idx == 0 ? seg_trace_key(s, row) : seg_span_key(s, row);
         default: return 0;
     }
 }
@@ -1387,7 +1315,7 @@ DEV bool eval_terms(const SegView& s, uint64_t row, const QuerySpec& q) {
 // A full table (every slot probed, none free or matching) yields
 // GROUP_FULL: the caller counts the row as overflow instead of merging it
 // into another group; the host reruns with a larger table.
-constexpr uint32_t GROUP_FULL = 0xFFFFFFFFu;
+constexpr uint32_t GROUP_FULL = ROW_NONE;
 
 DEV uint32_t group_claim(uint64_t h, const uint64_t* kraw, uint32_t n_keys,
                          uint64_t* gkeys, uint64_t* graw,
@@ -1799,18 +1727,12 @@ __global__ void k_unpack_bits(const uint32_t* __restrict__ packed,
     out[i] = base + (uint32_t)(v & mask);
 }
 
-inline uint32_t grid_for(uint64_t total) {
-    return (uint32_t)((total + BLOCK - 1) / BLOCK);
-}
-
 }  // namespace
 
 // ----------------------------------------------------------------------
 // C API (ctypes). All functions take the HIP stream as uint64 and return
 // hipError_t as int; launches are async on that stream.
 // ----------------------------------------------------------------------
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" {
 

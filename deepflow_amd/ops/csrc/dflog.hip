@@ -6,14 +6,11 @@
 // parsing into row columns, and a flat, bandwidth-bound scan of the pool per
 // query.
 //
-// Rules (same as dfgpu.hip / dfprofile.hip):
-//  - wave = 64 lanes; blocks are multiples of 64.
-//  - all cross-workgroup state uses device-scope atomics; no kernel reads
-//    in the same launch what another workgroup wrote with plain stores.
-//  - ids are SLOT INDICES: a claim is one atomicCAS on the 64-bit key. The
+// Rules: wave = 64 lanes, blocks are multiples of 64; table rules are in
+// dftable.h. Particular to this unit:
+//  - app ids are slot indices of a table probed from `h & mask`. The
 //    claimer alone writes the slot's metadata and nobody reads it before
 //    the next launch.
-//  - probe loops are bounded by the table size; EMPTY_KEY = 0 is reserved.
 //  - 64-bit hash identity is accepted for app names as it is for every
 //    other dictionary here.
 //
@@ -23,17 +20,11 @@
 // stages a fixed tile with 16-byte loads, tests every start position from
 // LDS and only maps the (rare) hits back to a row with a binary search over
 // body_off, which is non-decreasing in row index.
-#include <hip/hip_runtime.h>
 #include <string.h>
-#include "l7_layout.h"   // DICT_ID_INVALID
-
-#define DEV __device__ __forceinline__
-#include "dfhash.h"
+#include "dftable.h"
 
 namespace {
 
-constexpr uint64_t EMPTY_KEY = 0ull;
-constexpr uint32_t BLOCK = 256;
 constexpr uint64_t LOG_APP_SEED = 0x4C4F474150504944ull;    // "LOGAPPID"
 
 constexpr uint32_t LOG_TILE = 16384;        // match start positions per block
@@ -63,25 +54,6 @@ DEV uint32_t fold_ascii4(uint32_t x) {
     uint32_t gt = t + 0x25252525u;          // bit 7 set when byte >= 0x5b
     uint32_t m = ge & ~gt & ~x & 0x80808080u;
     return x | (m >> 2);
-}
-
-// probe-or-insert; returns slot, sets claimed when this thread inserted h
-DEV uint32_t log_probe(uint64_t h, uint64_t* tkeys, uint32_t cap_mask,
-                       bool& claimed) {
-    claimed = false;
-    uint32_t slot = (uint32_t)(h & cap_mask);
-    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-        uint64_t cur = tkeys[slot];
-        if (cur == h) return slot;
-        if (cur == EMPTY_KEY) {
-            uint64_t old = atomicCAS((unsigned long long*)&tkeys[slot],
-                                     EMPTY_KEY, h);
-            if (old == EMPTY_KEY) { claimed = true; return slot; }
-            if (old == h) return slot;
-        }
-        slot = (slot + 1) & cap_mask;
-    }
-    return DICT_ID_INVALID;
 }
 
 template <uint32_t N>
@@ -177,7 +149,8 @@ __global__ void k_log_ingest(const uint8_t* __restrict__ pool, uint64_t base,
 
     uint64_t h = str_hash(s + a_at, a_len, LOG_APP_SEED);
     bool claimed;
-    uint32_t aid = log_probe(h, apps.tkeys, apps.cap_mask, claimed);
+    uint32_t aid = table_claim(apps.tkeys, apps.cap_mask, h,
+                               (uint32_t)(h & apps.cap_mask), &claimed);
     if (aid == DICT_ID_INVALID) {
         atomicAdd(apps.drops, 1ull);
     } else if (claimed) {
@@ -367,13 +340,7 @@ void k_log_select(const int64_t* __restrict__ time,
     }
 }
 
-inline uint32_t grid_for(uint64_t total) {
-    return (uint32_t)((total + BLOCK - 1) / BLOCK);
-}
-
 }  // namespace
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" {
 

@@ -6,53 +6,24 @@
 // GPU, intern into a slot-index dictionary, keep columns in HBM, aggregate
 // at query time.
 //
-// Rules (same as dfgpu.hip):
-//  - wave = 64 lanes; blocks are multiples of 64.
-//  - all cross-workgroup state uses device-scope atomics; no kernel reads
-//    in the same launch what another workgroup wrote with plain stores.
-//  - ids are SLOT INDICES: a claim is one atomicCAS on the 64-bit key. The
-//    claimer alone writes the slot's metadata and nobody reads it before
-//    the next launch, so there is no second word to wait on.
-//  - probe loops are bounded by the table size; EMPTY_KEY = 0 is reserved.
+// Rules: wave = 64 lanes, blocks are multiples of 64; table rules are in
+// dftable.h. Particular to this unit:
+//  - stack ids and flame-node ids are slot indices of tables probed from
+//    `h & mask`. The claimer alone writes the slot's metadata and nobody
+//    reads it before the next launch.
 //  - 64-bit hash identity is accepted for stacks and for flame nodes
 //    exactly as it is for the SmartEncoding dictionary (dfgpu.hip K3): two
 //    different byte strings with one 64-bit hash would share an id.
-#include <hip/hip_runtime.h>
-#include "l7_layout.h"   // DICT_ID_INVALID
-
-#define DEV __device__ __forceinline__
-#include "dfhash.h"
+#include "dftable.h"
 
 namespace {
 
-constexpr uint64_t EMPTY_KEY = 0ull;
-constexpr uint32_t BLOCK = 256;
 constexpr uint64_t PROF_STACK_SEED = 0x50524F465354414Bull;  // "PROFSTAK"
 constexpr uint64_t PROF_FRAME_SEED = 0x50524F464652414Dull;  // "PROFFRAM"
 constexpr uint64_t PROF_ROOT_KEY = 0x524F4F54524F4F54ull;    // "ROOTROOT"
 
 DEV bool is_ws(uint8_t c) {  // bytes.strip(): space \t \n \v \f \r
     return c == 32 || (c >= 9 && c <= 13);
-}
-
-// probe-or-insert; returns slot, sets claimed when this thread inserted h.
-// Plain loads on the hit path (a stale EMPTY is corrected by the CAS).
-DEV uint32_t prof_probe(uint64_t h, uint64_t* tkeys, uint32_t cap_mask,
-                        bool& claimed) {
-    claimed = false;
-    uint32_t slot = (uint32_t)(h & cap_mask);
-    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-        uint64_t cur = tkeys[slot];
-        if (cur == h) return slot;
-        if (cur == EMPTY_KEY) {
-            uint64_t old = atomicCAS((unsigned long long*)&tkeys[slot],
-                                     EMPTY_KEY, h);
-            if (old == EMPTY_KEY) { claimed = true; return slot; }
-            if (old == h) return slot;
-        }
-        slot = (slot + 1) & cap_mask;
-    }
-    return DICT_ID_INVALID;
 }
 
 struct ProfStacks {
@@ -116,7 +87,8 @@ __global__ void k_prof_ingest(const uint8_t* __restrict__ buf,
     if (!skip) {
         uint64_t h = str_hash(s, len, PROF_STACK_SEED);
         bool claimed;
-        sid = prof_probe(h, st.tkeys, st.cap_mask, claimed);
+        sid = table_claim(st.tkeys, st.cap_mask, h,
+                          (uint32_t)(h & st.cap_mask), &claimed);
         if (sid == DICT_ID_INVALID) {
             atomicAdd(st.drops, 1ull);
         } else if (claimed) {
@@ -214,7 +186,8 @@ __global__ void k_flame_fold(const uint8_t* __restrict__ hit,
         if (h == EMPTY_KEY) h = 1;
         depth++;
         bool claimed;
-        uint32_t slot = prof_probe(h, nd.nkeys, nd.ncap_mask, claimed);
+        uint32_t slot = table_claim(nd.nkeys, nd.ncap_mask, h,
+                                    (uint32_t)(h & nd.ncap_mask), &claimed);
         if (slot == DICT_ID_INVALID) {
             atomicAdd(nd.drops, 1ull);
             return;
@@ -231,17 +204,12 @@ __global__ void k_flame_fold(const uint8_t* __restrict__ hit,
     }
 }
 
-inline uint32_t grid_for(uint64_t total) {
-    return (uint32_t)((total + BLOCK - 1) / BLOCK);
-}
-
 }  // namespace
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" {
 
 uint64_t df_prof_root_key() { return PROF_ROOT_KEY; }
+uint64_t df_prof_stack_seed() { return PROF_STACK_SEED; }
 
 int df_prof_ingest(const void* buf, const void* line_off,
                    const void* line_len, const void* line_msg,

@@ -15,31 +15,18 @@
 //                    block in LDS: a handful of groups fed by every row)
 // Only k_trace_extract sees segments; the rest read the flat arrays.
 //
-// Rules (same as dfgpu.hip / dfprofile.hip):
-//  - wave = 64 lanes; blocks are multiples of 64.
-//  - cross-workgroup state is written with device-scope atomics only, and
-//    no kernel reads in the same launch what another workgroup wrote.
-//  - a table slot is claimed with one atomicCAS on its 64-bit key; values
-//    are atomicMin/Max/Add words initialised by the host, so there is no
-//    second word to wait on.
-//  - probe loops are bounded by the table size; overflow is counted in
-//    `drops`, never waited out. EMPTY_KEY = 0 is reserved.
+// Rules: wave = 64 lanes, blocks are multiples of 64; table rules are in
+// dftable.h, segment access in dfseg.h. Particular to this unit:
+//  - no kernel reads in the same launch what another workgroup wrote.
+//  - table values are atomicMin/Max/Add words initialised by the host.
 //  - an index key is the 64-bit mix of (trace key, join key, relation); two
 //    different pairs with one mix would share a slot, the same 64-bit
 //    identity the dictionary and the flame nodes already accept.
-#include <hip/hip_runtime.h>
-#include "l7_layout.h"
-
-#define DEV __device__ __forceinline__
-#include "dfhash.h"
+#include "dftable.h"
+#include "dfseg.h"
 
 namespace {
 
-constexpr uint64_t EMPTY_KEY = 0ull;
-constexpr uint32_t BLOCK = 256;
-constexpr uint32_t ROW_NONE = 0xFFFFFFFFu;
-// seed of pooled-string filter hashes (dfgpu.hip STR_FILTER_SEED)
-constexpr uint64_t TRACE_STR_SEED = 0x5157A15E5EEDull;
 // depth walk bound; python twin query/tracemap.py MAX_TRACE_HOPS
 constexpr uint32_t MAX_TRACE_HOPS = 4096;
 
@@ -51,21 +38,6 @@ enum { TV_SPANS = 0, TV_ROOTS, TV_UNROOTED, TV_MAX_DEPTH, TV_ERRORS,
 // per-edge value words (python twin: tracemap.EV_*)
 enum { EV_CALLS = 0, EV_SPAN, EV_SYSCALL, EV_TCP, EV_ERRORS, EV_DUR_NS,
        EV_N };
-
-constexpr uint32_t STATUS_SERVER_ERROR = 3;
-constexpr uint32_t STATUS_CLIENT_ERROR = 4;
-
-struct TraceSeg {
-    const uint64_t* u64c;        // [L7_U64_N, stride]
-    const uint32_t* u32c;        // [L7_U32_N, stride]
-    const uint8_t* u8c;          // [L7_U8_N, stride]
-    const uint32_t* didc;        // [L7_DID_N, stride]
-    const uint64_t* str_rowref;  // [stride] (pool_off<<16 | total_len)
-    const int16_t* str_lens;     // [n_pool_cols, stride]
-    const uint8_t* pool;
-    uint64_t stride;
-    uint32_t n_rows;
-};
 
 // query-scoped flat columns, indexed by global row
 struct TraceFlat {
@@ -80,106 +52,44 @@ struct TraceFlat {
     uint8_t* status;    // response_status
 };
 
-// three first-row indexes, relation r at [r * cap, (r + 1) * cap)
-struct TraceIdx {
-    uint64_t* keys;
-    uint32_t* rows;              // host-initialised to ROW_NONE
-    unsigned long long* drops;
-    uint32_t cap;                // per relation, power of two
-};
-
+// three first-row indexes in one FirstRowIdx, relation r at
+// [r * cap, (r + 1) * cap)
 DEV uint64_t pair_key(uint64_t tkey, uint64_t k, uint32_t rel) {
     uint64_t h = mix64(mix64(tkey + rel) ^ k);
     return h ? h : 1ull;
 }
 
-// probe-or-insert; plain loads on the hit path (a stale EMPTY is corrected
-// by the CAS). Returns the slot, or ROW_NONE when the table is full.
-DEV uint32_t claim_slot(uint64_t h, uint64_t* tkeys, uint32_t cap_mask) {
-    uint32_t slot = (uint32_t)(mix64(h) & cap_mask);
-    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-        uint64_t cur = tkeys[slot];
-        if (cur == h) return slot;
-        if (cur == EMPTY_KEY) {
-            uint64_t old = atomicCAS((unsigned long long*)&tkeys[slot],
-                                     EMPTY_KEY, h);
-            if (old == EMPTY_KEY || old == h) return slot;
-        }
-        slot = (slot + 1) & cap_mask;
-    }
-    return ROW_NONE;
-}
-
-DEV void idx_insert(const TraceIdx& ix, uint32_t rel, uint64_t tkey,
+DEV void idx_insert(const FirstRowIdx& ix, uint32_t rel, uint64_t tkey,
                     uint64_t k, uint32_t row) {
-    uint64_t h = pair_key(tkey, k, rel);
-    uint64_t base = (uint64_t)rel * ix.cap;
-    uint32_t slot = claim_slot(h, ix.keys + base, ix.cap - 1);
-    if (slot == ROW_NONE) atomicAdd(ix.drops, 1ull);
-    else atomicMin(&ix.rows[base + slot], row);
+    first_row_insert(ix, (uint64_t)rel * ix.cap, pair_key(tkey, k, rel), row);
 }
 
-// read-only probe (a later launch than the inserts)
-DEV uint32_t idx_find(const TraceIdx& ix, uint32_t rel, uint64_t tkey,
+DEV uint32_t idx_find(const FirstRowIdx& ix, uint32_t rel, uint64_t tkey,
                       uint64_t k) {
-    uint64_t h = pair_key(tkey, k, rel);
-    uint64_t base = (uint64_t)rel * ix.cap;
-    uint32_t cap_mask = ix.cap - 1;
-    uint32_t slot = (uint32_t)(mix64(h) & cap_mask);
-    for (uint32_t probe = 0; probe <= cap_mask; probe++) {
-        uint64_t cur = ix.keys[base + slot];
-        if (cur == h) return ix.rows[base + slot];
-        if (cur == EMPTY_KEY) return ROW_NONE;
-        slot = (slot + 1) & cap_mask;
-    }
-    return ROW_NONE;
-}
-
-// pooled string `idx` of a row: pointer + length
-DEV const uint8_t* pool_str(const TraceSeg& s, uint64_t row, uint32_t idx,
-                            uint32_t& len) {
-    uint64_t off = STR_REF_OFF(s.str_rowref[row]);
-    for (uint32_t c = 0; c < idx; c++)
-        off += (uint16_t)s.str_lens[(uint64_t)c * s.stride + row];
-    len = (uint16_t)s.str_lens[(uint64_t)idx * s.stride + row];
-    return s.pool + off;
-}
-
-DEV uint64_t pool_hash(const TraceSeg& s, uint64_t row, uint32_t idx) {
-    uint32_t len;
-    const uint8_t* p = pool_str(s, row, idx, len);
-    return len ? str_hash(p, len, TRACE_STR_SEED) : 0;
+    return first_row_find(ix, (uint64_t)rel * ix.cap, pair_key(tkey, k, rel));
 }
 
 // one thread per segment row
-__global__ void k_trace_extract(TraceSeg s, uint32_t base_row,
+__global__ void k_trace_extract(SegView s, uint32_t base_row,
                                 uint64_t time_start, uint64_t time_end,
-                                TraceFlat f, TraceIdx ix) {
+                                TraceFlat f, FirstRowIdx ix) {
     uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= s.n_rows) return;
+    if (r >= (uint32_t)s.n_rows) return;
     uint32_t g = base_row + r;
     uint64_t start = s.u64c[(uint64_t)L7_U64_START_TIME * s.stride + r];
     uint64_t tkey = 0;
-    if (start >= time_start && start <= time_end) {
-        // the SRC_TRACE128 idx 0 value (dfgpu.hip src_value)
-        uint64_t hi = s.u64c[(uint64_t)L7_U64_TRACE_HI * s.stride + r];
-        uint64_t lo = s.u64c[(uint64_t)L7_U64_TRACE_LO * s.stride + r];
-        tkey = (hi | lo) ? (mix64(hi) ^ lo)
-                         : pool_hash(s, r, L7_POOL_TRACE_ID);
-    }
+    if (start >= time_start && start <= time_end) tkey = seg_trace_key(s, r);
     f.tkey[g] = tkey;
     if (tkey == 0) return;
-    // SRC_TRACE128 idx 1
-    uint64_t skey = s.u64c[(uint64_t)L7_U64_SPAN_ID_B * s.stride + r];
-    if (skey == 0) skey = pool_hash(s, r, L7_POOL_SPAN_ID);
+    uint64_t skey = seg_span_key(s, r);
     // parent id: the decoder's rule for span ids, applied to the pooled text
     uint32_t plen;
-    const uint8_t* pp = pool_str(s, r, L7_POOL_PARENT_SPAN_ID, plen);
+    const uint8_t* pp = seg_pool_str(s, r, L7_POOL_PARENT_SPAN_ID, plen);
     uint64_t pkey = 0;
     if (plen) {
         bool hex = plen == 16 && hex_parse64_with(
             [&](uint32_t i) -> uint8_t { return pp[i]; }, pkey);
-        if (!hex) pkey = str_hash(pp, plen, TRACE_STR_SEED);
+        if (!hex) pkey = str_hash(pp, plen, STR_FILTER_SEED);
     }
     uint64_t sreq = s.u64c[(uint64_t)L7_U64_SYSCALL_REQ * s.stride + r];
     uint64_t sresp = s.u64c[(uint64_t)L7_U64_SYSCALL_RESP * s.stride + r];
@@ -199,7 +109,7 @@ __global__ void k_trace_extract(TraceSeg s, uint32_t base_row,
 }
 
 // one thread per global row
-__global__ void k_trace_link(TraceFlat f, TraceIdx ix, uint32_t n,
+__global__ void k_trace_link(TraceFlat f, FirstRowIdx ix, uint32_t n,
                              uint32_t* __restrict__ parent,
                              uint8_t* __restrict__ kind) {
     uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
@@ -265,7 +175,8 @@ struct EdgeTable {
 
 DEV void edge_add_global(const EdgeTable& et, uint64_t key,
                          const unsigned long long* v) {
-    uint32_t slot = claim_slot(key, et.keys, et.cap_mask);
+    uint32_t slot = table_claim(et.keys, et.cap_mask, key,
+                                (uint32_t)(mix64(key) & et.cap_mask));
     if (slot == ROW_NONE) { atomicAdd(et.drops, v[EV_CALLS]); return; }
     unsigned long long* acc = et.vals + (uint64_t)slot * EV_N;
     for (int i = 0; i < EV_N; i++)
@@ -307,7 +218,8 @@ k_trace_fold(TraceFlat f, const uint32_t* __restrict__ parent,
         uint8_t st = f.status[g];
         bool err = st == STATUS_SERVER_ERROR || st == STATUS_CLIENT_ERROR;
         uint64_t start = f.start[g], end = f.end[g];
-        uint32_t slot = claim_slot(tkey, tkeys, tcap_mask);
+        uint32_t slot = table_claim(tkeys, tcap_mask, tkey,
+                                    (uint32_t)(mix64(tkey) & tcap_mask));
         if (slot == ROW_NONE) {
             atomicAdd(tdrops, 1ull);
         } else {
@@ -359,13 +271,13 @@ k_trace_fold(TraceFlat f, const uint32_t* __restrict__ parent,
     }
 }
 
-inline uint32_t grid_for(uint64_t total, uint32_t per_block = BLOCK) {
-    return (uint32_t)((total + per_block - 1) / per_block);
+inline TraceFlat flat_of(const uint64_t* p) {
+    return TraceFlat{(uint64_t*)p[0], (uint64_t*)p[1], (uint64_t*)p[2],
+                     (uint64_t*)p[3], (uint64_t*)p[4], (uint32_t*)p[5],
+                     (uint32_t*)p[6], (uint8_t*)p[7], (uint8_t*)p[8]};
 }
 
 }  // namespace
-
-#define STREAM(s) reinterpret_cast<hipStream_t>(s)
 
 extern "C" {
 
@@ -380,18 +292,21 @@ int df_trace_extract(const void* u64c, const void* u32c, const void* u8c,
                      const uint64_t* flat, void* idx_keys, void* idx_rows,
                      void* drops, uint32_t idx_cap, uint64_t stream) {
     if (n_rows == 0) return 0;
-    TraceSeg s{(const uint64_t*)u64c, (const uint32_t*)u32c,
-               (const uint8_t*)u8c, (const uint32_t*)didc,
-               (const uint64_t*)str_rowref, (const int16_t*)str_lens,
-               (const uint8_t*)pool, stride, n_rows};
-    TraceFlat f{(uint64_t*)flat[0], (uint64_t*)flat[1], (uint64_t*)flat[2],
-                (uint64_t*)flat[3], (uint64_t*)flat[4], (uint32_t*)flat[5],
-                (uint32_t*)flat[6], (uint8_t*)flat[7], (uint8_t*)flat[8]};
-    TraceIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows,
-                (unsigned long long*)drops, idx_cap};
+    SegView s{};
+    s.u64c = (const uint64_t*)u64c;
+    s.u32c = (const uint32_t*)u32c;
+    s.u8c = (const uint8_t*)u8c;
+    s.didc = (const uint32_t*)didc;
+    s.str_rowref = (const uint64_t*)str_rowref;
+    s.str_lens = (const int16_t*)str_lens;
+    s.pool = (const uint8_t*)pool;
+    s.stride = stride;
+    s.n_rows = n_rows;
+    FirstRowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows,
+                   (unsigned long long*)drops, idx_cap};
     hipLaunchKernelGGL(k_trace_extract, dim3(grid_for(n_rows)), dim3(BLOCK),
                        0, STREAM(stream), s, base_row, time_start, time_end,
-                       f, ix);
+                       flat_of(flat), ix);
     return (int)hipGetLastError();
 }
 
@@ -399,12 +314,11 @@ int df_trace_link(const uint64_t* flat, const void* idx_keys,
                   const void* idx_rows, uint32_t idx_cap, uint32_t n,
                   void* parent, void* kind, uint64_t stream) {
     if (n == 0) return 0;
-    TraceFlat f{(uint64_t*)flat[0], (uint64_t*)flat[1], (uint64_t*)flat[2],
-                (uint64_t*)flat[3], (uint64_t*)flat[4], (uint32_t*)flat[5],
-                (uint32_t*)flat[6], (uint8_t*)flat[7], (uint8_t*)flat[8]};
-    TraceIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows, nullptr, idx_cap};
+    FirstRowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows, nullptr,
+                   idx_cap};
     hipLaunchKernelGGL(k_trace_link, dim3(grid_for(n)), dim3(BLOCK), 0,
-                       STREAM(stream), f, ix, n, (uint32_t*)parent,
+                       STREAM(stream), flat_of(flat), ix, n,
+                       (uint32_t*)parent,
                        (uint8_t*)kind);
     return (int)hipGetLastError();
 }
@@ -423,14 +337,12 @@ int df_trace_fold(const uint64_t* flat, const void* parent, const void* kind,
                   uint32_t tcap, void* ekeys, void* evals, uint32_t ecap,
                   void* drops, uint64_t stream) {
     if (n == 0) return 0;
-    TraceFlat f{(uint64_t*)flat[0], (uint64_t*)flat[1], (uint64_t*)flat[2],
-                (uint64_t*)flat[3], (uint64_t*)flat[4], (uint32_t*)flat[5],
-                (uint32_t*)flat[6], (uint8_t*)flat[7], (uint8_t*)flat[8]};
     EdgeTable et{(uint64_t*)ekeys, (unsigned long long*)evals,
                  (unsigned long long*)drops, ecap - 1};
     hipLaunchKernelGGL(k_trace_fold,
                        dim3(grid_for(n, FOLD_ROWS_PER_BLOCK)), dim3(BLOCK),
-                       0, STREAM(stream), f, (const uint32_t*)parent,
+                       0, STREAM(stream), flat_of(flat),
+                       (const uint32_t*)parent,
                        (const uint8_t*)kind, (const int32_t*)depth, n,
                        (uint64_t*)tkeys, (unsigned long long*)tvals,
                        tcap - 1, (unsigned long long*)drops, et);

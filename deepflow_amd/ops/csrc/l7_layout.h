@@ -151,6 +151,11 @@ enum {
 #define L7_POOL_X_REQUEST_ID_0 5
 #define L7_POOL_X_REQUEST_ID_1 6
 
+// L7_U8_STATUS values that count as errors (python twin:
+// wire/const_enums.py)
+#define STATUS_SERVER_ERROR 3u
+#define STATUS_CLIENT_ERROR 4u
+
 #define DICT_ID_INVALID 0xFFFFFFFFu
 #define STR_REF_PACK(off, len) \
     ((((uint64_t)(off)) << 16) | ((len) > 0xFFFFu ? 0xFFFFu : (uint64_t)(len)))

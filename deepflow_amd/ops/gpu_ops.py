@@ -8,6 +8,9 @@ by the device='cpu' pipeline).
 """
 from __future__ import annotations
 
+import ctypes
+
+import numpy as np
 import torch
 
 from . import native
@@ -46,7 +49,6 @@ def rollup_family(seg, base_row: int, n: int, time_base_s: int, tables,
                   stream: int = 0) -> None:
     """ONE fused launch updates every table of a family (k_rollup_l4/l7
     iterate the per-table key specs over a single pass of the row)."""
-    import numpy as np
     lib = native.gpu()
     src = tables[0].td.source
     fn = lib.df_rollup_l4 if src == "l4" else lib.df_rollup_l7
@@ -77,7 +79,6 @@ def rollup_insert(kws: torch.Tensor, vals: torch.Tensor, ops: torch.Tensor,
 def sort_u64(data: torch.Tensor) -> None:
     """In-place rocPRIM radix sort of a device int64 tensor (values
     treated as u64)."""
-    import ctypes
     lib = native.gpu()
     n = data.numel()
     if n == 0:
@@ -168,10 +169,32 @@ def pool_gather(payload: torch.Tensor, seg, pool_cols: torch.Tensor,
         "df_pool_gather")
 
 
-
 def _opt_ptr(seg, attr: str) -> int:
     t = getattr(seg, attr, None)
     return t.data_ptr() if t is not None else 0
+
+
+def _kg_args(kg):
+    """KnowledgeGraph table pointers for the query-time join."""
+    if kg is None:
+        return 0, 0, 0
+    return kg.tkeys.data_ptr(), kg.tvals.data_ptr(), kg.tkeys.numel()
+
+
+def _seg_cols(seg):
+    return seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr()
+
+
+def _seg_pool(seg):
+    return (seg.str_rowref.data_ptr(), seg.str_lens.data_ptr(),
+            seg.pool.data_ptr(), seg.capacity, seg.n_rows)
+
+
+def _seg_args(seg, kg):
+    """The leading segment arguments of the three query entry points."""
+    return (*_seg_cols(seg), _opt_ptr(seg, "did"), *_kg_args(kg),
+            _opt_ptr(seg, "attr_pool"), _opt_ptr(seg, "attr_start"),
+            _opt_ptr(seg, "attr_cnt"), *_seg_pool(seg))
 
 
 def query_agg(seg, spec_bytes: bytes, base_row: int, n: int,
@@ -182,17 +205,10 @@ def query_agg(seg, spec_bytes: bytes, base_row: int, n: int,
     found no free slot in the group table. They are left out of every
     reported group, so a non-zero count means 'rerun with a larger
     table'."""
-    import ctypes
     lib = native.gpu()
     buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
-    ktk, ktv, kcap = _kg_args(kg)
     native.check(lib.df_query_agg(
-        seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr(),
-        _opt_ptr(seg, "did"), ktk, ktv, kcap, _opt_ptr(seg, "attr_pool"),
-        _opt_ptr(seg, "attr_start"), _opt_ptr(seg, "attr_cnt"),
-        seg.str_rowref.data_ptr(), seg.str_lens.data_ptr(),
-        seg.pool.data_ptr(), seg.capacity, seg.n_rows,
-        ctypes.addressof(buf), n, base_row,
+        *_seg_args(seg, kg), ctypes.addressof(buf), n, base_row,
         gkeys.data_ptr(), graw.data_ptr(), gvals.data_ptr(), gkeys.numel(),
         overflow.data_ptr(), _stream()), "df_query_agg")
 
@@ -206,45 +222,24 @@ def qpart_agg(seg, spec_bytes: bytes, base_row: int, n: int,
     """Radix-partitioned group-by (high key cardinality): bucket rows by
     8 hash bits, aggregate one bucket per workgroup set — each block's
     LDS table then holds every key it sees (no per-row global atomics).
-    counts/cursors: u32[256] (counts zeroed); row_scratch:\n    u64[n * (n_keys+n_aggs)] payload staging; overflow: as in
-    query_agg."""
-    import ctypes
+    counts/cursors: u32[256] (counts zeroed); row_scratch:
+    u64[n * (n_keys+n_aggs)] payload staging; overflow: as in query_agg."""
     lib = native.gpu()
     buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
-    ktk, ktv, kcap = _kg_args(kg)
     native.check(lib.df_qpart_agg(
-        seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr(),
-        _opt_ptr(seg, "did"), ktk, ktv, kcap, _opt_ptr(seg, "attr_pool"),
-        _opt_ptr(seg, "attr_start"), _opt_ptr(seg, "attr_cnt"),
-        seg.str_rowref.data_ptr(), seg.str_lens.data_ptr(),
-        seg.pool.data_ptr(), seg.capacity, seg.n_rows,
-        ctypes.addressof(buf), n, base_row,
+        *_seg_args(seg, kg), ctypes.addressof(buf), n, base_row,
         counts.data_ptr(), cursors.data_ptr(), row_scratch.data_ptr(),
         gkeys.data_ptr(), graw.data_ptr(), gvals.data_ptr(),
         gkeys.numel(), overflow.data_ptr(), _stream()), "df_qpart_agg")
 
 
-def _kg_args(kg):
-    """KnowledgeGraph table pointers for the query-time join."""
-    if kg is None:
-        return 0, 0, 0
-    return kg.tkeys.data_ptr(), kg.tvals.data_ptr(), kg.tkeys.numel()
-
-
 def query_select(seg, spec_bytes: bytes, base_row: int, n: int,
                  out_rows: torch.Tensor, out_ctr: torch.Tensor,
                  kg=None) -> None:
-    import ctypes
     lib = native.gpu()
     buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
-    ktk, ktv, kcap = _kg_args(kg)
     native.check(lib.df_query_select(
-        seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr(),
-        _opt_ptr(seg, "did"), ktk, ktv, kcap, _opt_ptr(seg, "attr_pool"),
-        _opt_ptr(seg, "attr_start"), _opt_ptr(seg, "attr_cnt"),
-        seg.str_rowref.data_ptr(), seg.str_lens.data_ptr(),
-        seg.pool.data_ptr(), seg.capacity, seg.n_rows,
-        ctypes.addressof(buf), n, base_row,
+        *_seg_args(seg, kg), ctypes.addressof(buf), n, base_row,
         out_rows.data_ptr(), out_ctr.data_ptr(), out_rows.numel(), _stream()),
         "df_query_select")
 
@@ -311,10 +306,8 @@ def trace_extract(seg, base_row: int, time_start: int, time_end: int,
                   ws) -> None:
     lib = native.gpu()
     native.check(lib.df_trace_extract(
-        seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr(),
-        seg.did.data_ptr(), seg.str_rowref.data_ptr(),
-        seg.str_lens.data_ptr(), seg.pool.data_ptr(), seg.capacity,
-        seg.n_rows, base_row, time_start, time_end,
+        *_seg_cols(seg), seg.did.data_ptr(), *_seg_pool(seg), base_row,
+        time_start, time_end,
         ws.flat_ptrs.ctypes.data, ws.idx_keys.data_ptr(),
         ws.idx_rows.data_ptr(), ws.drops.data_ptr(), ws.idx_cap,
         _stream()), "df_trace_extract")
@@ -354,10 +347,8 @@ def flow_extract(seg, base_row: int, time_start: int, time_end: int,
                  ws) -> None:
     lib = native.gpu()
     native.check(lib.df_flow_extract(
-        seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr(),
-        seg.str_rowref.data_ptr(), seg.str_lens.data_ptr(),
-        seg.pool.data_ptr(), seg.capacity, seg.n_rows, base_row,
-        time_start, time_end, ws.flat_ptrs.ctypes.data,
+        *_seg_cols(seg), *_seg_pool(seg), base_row, time_start, time_end,
+        ws.flat_ptrs.ctypes.data,
         ws.idx_keys.data_ptr(), ws.idx_rows.data_ptr(),
         ws.drops.data_ptr(), ws.idx_cap, _stream()), "df_flow_extract")
 
@@ -423,7 +414,6 @@ def log_ingest(st, base: int, line_off: torch.Tensor, line_len: torch.Tensor,
 def log_scan(st, needles, fold: bool, mask: torch.Tensor) -> None:
     """OR bit k into mask[row] for every row whose body holds needles[k]
     (bytes, 1..128 each, at most 8; already folded when fold is set)."""
-    import numpy as np
     if not needles:
         return
     lib = native.gpu()

@@ -57,7 +57,8 @@ from ..store import l7_schema as S
 from ..wire.const_enums import STATUS_CLIENT_ERROR, STATUS_SERVER_ERROR
 from .spec import SRC_TRACE128, STR_FILTER_SEED
 from .tags import L7_TAGS
-from .tracemap import M32, U64MAX, TraceMapper, _pow2_at_least
+from .tracemap import (M32, U64MAX, TraceMapper, _pow2_at_least,
+                       _timed_launches, pool_strings)
 
 # key spaces (twin: dfflow.hip REL_*); bit r of `via` = space r
 REL_TRACE, REL_SYSCALL, REL_TCP, REL_XREQ, REL_N = range(5)
@@ -111,18 +112,9 @@ def xreq_key_of(x_request_id: str) -> int:
 def _pool_hash_np(seg, n: int, idx: int) -> np.ndarray:
     """Pooled-string hash of pool column `idx`, 0 where it is empty."""
     from ..store.dictionary import str_hash_py
-    rowref = seg.str_rowref[:n].numpy().view(np.uint64)
-    lens = seg.str_lens[:, :n].numpy().view(np.uint16)
     out = np.zeros(n, dtype=np.uint64)
-    hit = np.nonzero(lens[idx])[0]
-    if len(hit) == 0:
-        return out
-    pool = seg.pool.numpy().tobytes()
-    before = lens[:idx].astype(np.int64).sum(axis=0)
-    for i in hit:
-        off = (int(rowref[i]) >> 16) + int(before[i])
-        out[i] = str_hash_py(pool[off:off + int(lens[idx, i])],
-                             STR_FILTER_SEED)
+    for i, raw in pool_strings(seg, n, idx):
+        out[i] = str_hash_py(raw, STR_FILTER_SEED)
     return out
 
 
@@ -273,37 +265,21 @@ class FlowGrouper:
         self.kernel_ms: Optional[Dict[str, float]] = None
 
     # ------------------------------------------------------------ plumbing
-    def _on_gpu(self) -> bool:
-        return not str(self.engine.device).startswith("cpu")
-
     def _gpu_run(self, segs, bases, lo: int, hi: int, fold: bool):
         from ..ops import gpu_ops
         dev = segs[0].u64.device
         ws = _FlowWorkspace(int(bases[-1]), dev)
-        ms = self.kernel_ms
-        marks = []
-
-        def mark(name):
-            if ms is not None:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record()
-                marks.append((name, ev))
-
-        mark("start")
-        for seg, base in zip(segs, bases):
-            gpu_ops.flow_extract(seg, int(base), lo, hi, ws)
-        mark("extract")
-        gpu_ops.flow_union(ws)
-        mark("union")
-        gpu_ops.flow_flatten(ws)
-        mark("flatten")
-        if fold:
-            gpu_ops.flow_fold(ws)
-            mark("fold")
-        if ms is not None:
-            torch.cuda.synchronize()
-            for (_, a), (name, b) in zip(marks, marks[1:]):
-                ms[name] = a.elapsed_time(b)
+        with _timed_launches(self.kernel_ms) as mark:
+            for seg, base in zip(segs, bases):
+                gpu_ops.flow_extract(seg, int(base), lo, hi, ws)
+            mark("extract")
+            gpu_ops.flow_union(ws)
+            mark("union")
+            gpu_ops.flow_flatten(ws)
+            mark("flatten")
+            if fold:
+                gpu_ops.flow_fold(ws)
+                mark("fold")
         return ws
 
     def _host_flat(self, segs, lo, hi) -> _Flat:
@@ -320,7 +296,7 @@ class FlowGrouper:
                 segs, bases = self._tm._scan(lo, hi)
                 if not segs:
                     return _empty_links()
-                if self._on_gpu():
+                if self._tm._on_gpu():
                     ws = self._gpu_run(segs, bases, lo, hi, fold=False)
                     rows = torch.nonzero(ws.part).view(-1)
                     packed = torch.stack([
@@ -349,7 +325,7 @@ class FlowGrouper:
                 if not segs:
                     return {"groups": [], "group_count": 0, "span_count": 0,
                             "drops": 0}
-                if self._on_gpu():
+                if self._tm._on_gpu():
                     ws = self._gpu_run(segs, bases, lo, hi, fold=True)
                     gid, gv, drops = self._read_gpu_table(ws, min_spans)
                 else:
@@ -392,7 +368,7 @@ class FlowGrouper:
                 segs, bases = self._tm._scan(lo, hi)
                 if not segs or key == 0:
                     return empty
-                if self._on_gpu():
+                if self._tm._on_gpu():
                     ws = self._gpu_run(segs, bases, lo, hi, fold=False)
                     part = ws.part != 0
                     k = torch.tensor(key - (1 << 64) if key >> 63 else key,

@@ -32,6 +32,7 @@ kernels. There is no fallback between the two.
 """
 from __future__ import annotations
 
+import contextlib
 from typing import Dict, List, Optional
 
 import numpy as np
@@ -64,21 +65,50 @@ def _pow2_at_least(n: int) -> int:
     return 1 << max(int(n) - 1, 1).bit_length()
 
 
+def pool_strings(seg, n: int, idx: int):
+    """(row, bytes) of every non-empty string in pool column `idx` among
+    the first n rows of a host segment (twin: dfseg.h seg_pool_str)."""
+    lens = seg.str_lens[:, :n].numpy().view(np.uint16)
+    hit = np.nonzero(lens[idx])[0]
+    if len(hit) == 0:
+        return
+    rowref = seg.str_rowref[:n].numpy().view(np.uint64)
+    pool = seg.pool.numpy().tobytes()
+    before = lens[:idx].astype(np.int64).sum(axis=0)
+    for i in hit:
+        off = (int(rowref[i]) >> 16) + int(before[i])
+        yield i, pool[off:off + int(lens[idx, i])]
+
+
 def _parent_keys_np(seg, n: int) -> np.ndarray:
     from ..ops.ref import hex_parse64_py
     from ..store.dictionary import str_hash_py
-    idx = S.POOL_POS["parent_span_id"]
-    rowref = seg.str_rowref[:n].numpy().view(np.uint64)
-    lens = seg.str_lens[:, :n].numpy().view(np.uint16)
-    pool = seg.pool.numpy().tobytes()
     out = np.zeros(n, dtype=np.uint64)
-    before = lens[:idx].astype(np.int64).sum(axis=0)
-    for i in np.nonzero(lens[idx])[0]:
-        off = (int(rowref[i]) >> 16) + int(before[i])
-        raw = pool[off:off + int(lens[idx, i])]
+    for i, raw in pool_strings(seg, n, S.POOL_POS["parent_span_id"]):
         v = hex_parse64_py(raw)
         out[i] = str_hash_py(raw, STR_FILTER_SEED) if v is None else v
     return out
+
+
+@contextlib.contextmanager
+def _timed_launches(kernel_ms: Optional[Dict[str, float]]):
+    """Yields mark(name), to be called after each group of launches. With a
+    dict, the milliseconds since the previous mark land under `name` (one
+    event pair per mark); with None, marks cost nothing."""
+    marks = []
+
+    def mark(name):
+        if kernel_ms is not None:
+            ev = torch.cuda.Event(enable_timing=True)
+            ev.record()
+            marks.append((name, ev))
+
+    mark("start")
+    yield mark
+    if kernel_ms is not None:
+        torch.cuda.synchronize()
+        for (_, a), (name, b) in zip(marks, marks[1:]):
+            kernel_ms[name] = a.elapsed_time(b)
 
 
 class _Flat:
@@ -285,30 +315,17 @@ class TraceMapper:
         from ..ops import gpu_ops
         dev = segs[0].u64.device
         ws = _GpuWorkspace(int(bases[-1]), dev)
-        ms = self.kernel_ms
-        marks = []
-
-        def mark(name):
-            if ms is not None:
-                ev = torch.cuda.Event(enable_timing=True)
-                ev.record()
-                marks.append((name, ev))
-
-        mark("start")
-        for seg, base in zip(segs, bases):
-            gpu_ops.trace_extract(seg, int(base), lo, hi, ws)
-        mark("extract")
-        gpu_ops.trace_link(ws)
-        mark("link")
-        gpu_ops.trace_depth(ws)
-        mark("depth")
-        if fold:
-            gpu_ops.trace_fold(ws)
-            mark("fold")
-        if ms is not None:
-            torch.cuda.synchronize()
-            for (_, a), (name, b) in zip(marks, marks[1:]):
-                ms[name] = a.elapsed_time(b)
+        with _timed_launches(self.kernel_ms) as mark:
+            for seg, base in zip(segs, bases):
+                gpu_ops.trace_extract(seg, int(base), lo, hi, ws)
+            mark("extract")
+            gpu_ops.trace_link(ws)
+            mark("link")
+            gpu_ops.trace_depth(ws)
+            mark("depth")
+            if fold:
+                gpu_ops.trace_fold(ws)
+                mark("fold")
         return ws
 
     def _trace_ids(self, segs, bases, rows: np.ndarray) -> List[str]:

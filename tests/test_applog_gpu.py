@@ -80,6 +80,30 @@ def test_growth_reallocates_rows_and_pool(parse_host):
     same_search(parse_host, gpu, "ot")
 
 
+def test_app_ids_are_home_slots():
+    """An app id is the slot the probe starts at, `hash & (cap - 1)`, when
+    that slot is free. cap = 4 is the smallest power of two with room for
+    three distinct home slots."""
+    from deepflow_amd.store.dictionary import str_hash_py
+    seed, cap = int(native.gpu().df_log_app_seed()), 4
+    apps, homes = [], []
+    for i in range(64):
+        a = b"app%d" % i
+        home = str_hash_py(a, seed) & (cap - 1)
+        if home not in homes:
+            apps.append(a)
+            homes.append(home)
+        if len(apps) == 3:
+            break
+    assert len(set(homes)) == len(apps) == 3
+    data = b"\n".join(b"%d info %s body" % (i + 1, a)
+                      for i, a in enumerate(apps))
+    gpu, _ = gpu_of([("lines", data, 0, "s")], app_capacity=cap)
+    assert gpu.store.app_drops == 0
+    assert gpu.store.row_app[:3].tolist() == homes
+    assert [r["app_service"] for r in gpu.rows] == [a.decode() for a in apps]
+
+
 def test_full_app_table_counts_drops():
     calls = [
         ("lines", b"1 info a1 one\n2 info a2 two\n3 info a1 three", 0, "s"),

@@ -226,6 +226,35 @@ def test_shared_prefix_under_contention():
     assert gpu.store.n_stacks == 512
 
 
+def test_stack_ids_are_home_slots():
+    """A stack id is the slot the probe starts at, `hash & (cap - 1)`, when
+    that slot is free. cap = 4 is the smallest power of two with room for
+    three distinct home slots."""
+    import ctypes
+    from deepflow_amd.ops import native
+    from deepflow_amd.store.dictionary import str_hash_py
+    seed_fn = native.gpu().df_prof_stack_seed
+    seed_fn.restype, seed_fn.argtypes = ctypes.c_uint64, []
+    seed, cap = int(seed_fn()), 4
+    stacks, homes = [], []
+    for i in range(64):
+        s = b"frame%d" % i
+        home = str_hash_py(s, seed) & (cap - 1)
+        if home not in homes:
+            stacks.append(s)
+            homes.append(home)
+        if len(stacks) == 3:
+            break
+    assert len(set(homes)) == len(stacks) == 3
+    gpu = ProfilePipeline(device="cuda", stack_capacity=cap)
+    data = b"\n".join(s + b" 1" for s in stacks)
+    gpu.ingest_payload(payload_of([msg(data)]))
+    st = gpu.store
+    assert st.n_rows == 3 and st.stack_drops == 0
+    assert st.row_stack[:3].tolist() == homes
+    assert st.id_to_loc == stacks
+
+
 def test_full_stack_table_is_bounded():
     value = {f"s{i};t".encode(): i + 1 for i in range(12)}
     data = b"\n".join(k + b" " + str(v).encode() for k, v in value.items())

@@ -88,6 +88,7 @@ class L7IngestPipeline:
         # persist into segments)
         self._scratch_str = None
         self._scratch_attr = None
+        self._held_inputs = None  # see _run_gpu
         # async bookkeeping (GPU mode): naive-bytes accounting accumulates
         # on-device; dictionary harvest is deferred behind an event so the
         # steady state (no new strings) costs zero host syncs
@@ -180,6 +181,15 @@ class L7IngestPipeline:
         cum = torch.cumsum(row_len.to(torch.int64), 0)
         totals = torch.stack((acum[-1], cum[-1])).cpu()
         attr_total, total = int(totals[0]), int(totals[1])
+        # hold this batch's device tensors until the next batch gets here.
+        # The caller may drop them on return while intern_attrs and
+        # pool_gather below still read the payload; one that stages the
+        # next batch on a copy stream of its own would get the same block
+        # back from the caching allocator and overwrite it under them (the
+        # allocator orders reuse on the allocating stream only). The sync
+        # above means every kernel of the previous batch is done, so this
+        # is where its tensors can go.
+        self._held_inputs = (payload_t, offs_t, lens_t)
         seg.ensure_attr_pool(attr_total)
         starts = (acum - cnts + seg.attr_pool_len).to(torch.int32)
         seg.attr_start[base:base + n] = starts

@@ -886,6 +886,57 @@ __global__ void k_rollup_insert(const uint64_t* __restrict__ kws,  // [n, nw]
     }
 }
 
+// Interval flush without a host round trip: one grid-stride pass packs
+// every occupied slot of a table into dense staging rows (out_keys [cap,
+// nw], out_vals [cap, nv]; order undefined, readers sort and merge) and
+// puts every slot back into its freshly constructed state: tkeys 0, tvals
+// 0, all RU_MAX_KEYS words of traw the sentinel, so ru_claim_h never sees
+// a stale word 0 behind a reused hash. hdr[0] counts the rows written
+// (one atomicAdd per wave: ballot + prefix popcount), hdr[1] takes the
+// drops counter; hdr is zero on entry. Stream order is the only
+// synchronisation: no rollup kernel runs alongside.
+__global__ void __launch_bounds__(256)
+k_rollup_drain(uint64_t* __restrict__ tkeys, uint64_t* __restrict__ traw,
+               unsigned long long* __restrict__ tvals,
+               unsigned long long* __restrict__ drops,
+               uint32_t cap, uint32_t nw, uint32_t nv,
+               uint64_t* __restrict__ out_keys,
+               unsigned long long* __restrict__ out_vals,
+               unsigned long long* __restrict__ hdr) {
+    const uint32_t lane = threadIdx.x & 63u;
+    const uint64_t stride_g = (uint64_t)gridDim.x * blockDim.x;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        hdr[1] = *drops;
+        *drops = 0;
+    }
+    // base is the slot of the wave's lane 0, so the loop bound is
+    // wave-uniform and all 64 lanes reach the ballot together
+    for (uint64_t base = (uint64_t)blockIdx.x * blockDim.x +
+                         (threadIdx.x - lane);
+         base < cap; base += stride_g) {
+        const uint64_t slot = base + lane;
+        const bool in = slot < cap;
+        const bool live = in && tkeys[slot] != EMPTY_KEY;
+        const unsigned long long m = __ballot(live);
+        unsigned long long first = 0;
+        if (lane == 0 && m)
+            first = atomicAdd(&hdr[0], (unsigned long long)__popcll(m));
+        first = __shfl(first, 0);
+        uint64_t* r = &traw[slot * RU_MAX_KEYS];
+        unsigned long long* a = &tvals[slot * nv];
+        if (live) {
+            const uint64_t o = first + __popcll(m & ((1ull << lane) - 1ull));
+            for (uint32_t w = 0; w < nw; w++) out_keys[o * nw + w] = r[w];
+            for (uint32_t v = 0; v < nv; v++) out_vals[o * nv + v] = a[v];
+        }
+        if (in) {
+            tkeys[slot] = EMPTY_KEY;
+            for (uint32_t w = 0; w < RU_MAX_KEYS; w++) r[w] = RU_SENTINEL;
+            for (uint32_t v = 0; v < nv; v++) a[v] = 0;
+        }
+    }
+}
+
 // ----------------------------------------------------------------------
 // Data-plane shard routing: gather selected records into a packed
 // per-destination buffer for the RCCL all-to-all (one wave per record,
@@ -1809,6 +1860,26 @@ int df_rollup_insert(const void* kws, const void* vals, const void* ops,
                        (const uint8_t*)ops, n, nw, nv, (uint64_t*)tkeys,
                        (uint64_t*)traw, (unsigned long long*)tvals, cap - 1,
                        (unsigned long long*)drops);
+    return (int)hipGetLastError();
+}
+
+// hdr: u64[2], zero on entry; out_keys [cap, nw], out_vals [cap, nv]
+int df_rollup_drain(void* tkeys, void* traw, void* tvals, void* drops,
+                    uint32_t cap, uint32_t nw, uint32_t nv,
+                    void* out_keys, void* out_vals, void* hdr,
+                    uint64_t stream) {
+    if (cap == 0 || (cap & (cap - 1)) != 0 || nw == 0 || nw > RU_MAX_KEYS)
+        return (int)hipErrorInvalidValue;
+    // a few waves per SIMD on every CU; the pass is a plain stream over
+    // the table, so more blocks than that only add launch overhead
+    uint32_t blocks = grid_for(cap);
+    if (blocks > 2048) blocks = 2048;
+    hipLaunchKernelGGL(k_rollup_drain, dim3(blocks), dim3(BLOCK), 0,
+                       STREAM(stream), (uint64_t*)tkeys, (uint64_t*)traw,
+                       (unsigned long long*)tvals,
+                       (unsigned long long*)drops, cap, nw, nv,
+                       (uint64_t*)out_keys, (unsigned long long*)out_vals,
+                       (unsigned long long*)hdr);
     return (int)hipGetLastError();
 }
 

@@ -76,6 +76,20 @@ def rollup_insert(kws: torch.Tensor, vals: torch.Tensor, ops: torch.Tensor,
         stream or _stream()), "df_rollup_insert")
 
 
+def rollup_drain(table, out_keys: torch.Tensor, out_vals: torch.Tensor,
+                 hdr: torch.Tensor, stream: int = 0) -> None:
+    """Pack the table's occupied slots into out_keys [cap, nw] / out_vals
+    [cap, nv] and reset the table, all on the stream. hdr: i64[2], zeroed
+    by the caller; receives (rows written, drops). No host sync."""
+    lib = native.gpu()
+    native.check(lib.df_rollup_drain(
+        table.tkeys.data_ptr(), table.traw.data_ptr(),
+        table.tvals.data_ptr(), table.drops.data_ptr(),
+        table.capacity, table.nw, table.nv,
+        out_keys.data_ptr(), out_vals.data_ptr(), hdr.data_ptr(),
+        stream or _stream()), "df_rollup_drain")
+
+
 def sort_u64(data: torch.Tensor) -> None:
     """In-place rocPRIM radix sort of a device int64 tensor (values
     treated as u64)."""

@@ -118,6 +118,8 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_rollup_insert.restype = ct.c_int
     lib.df_rollup_insert.argtypes = [p, p, p, u32, u32, u32, p, p, p, u32,
                                      p, u64]
+    lib.df_rollup_drain.restype = ct.c_int
+    lib.df_rollup_drain.argtypes = [p, p, p, p, u32, u32, u32, p, p, p, u64]
     lib.df_gather_records.restype = ct.c_int
     lib.df_gather_records.argtypes = [p, p, p, p, p, u32, p, u64]
     lib.df_kg_build.restype = ct.c_int

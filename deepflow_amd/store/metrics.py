@@ -19,6 +19,8 @@ the numerics oracle for the GPU tests.
 from __future__ import annotations
 
 import struct
+import threading
+from collections import deque
 
 import numpy as np
 from dataclasses import dataclass
@@ -173,9 +175,87 @@ def _np_merge(keys: "np.ndarray", vals: "np.ndarray", ops):
     return uniq, out
 
 
+class _DrainLander:
+    """Brings queued GPU drains to the host off the ingest thread.
+
+    flush_live launches the drain kernel, records an event and submits
+    (table, event) here; a worker thread waits on the event and copies the
+    packed rows into the table's archive on a stream of its own, so the
+    ingest thread never waits for a flush it queued — only settle() does.
+    Jobs land in submission order. The worker starts with the first queued
+    job and ends when the queue runs empty, so an idle lander holds no
+    thread and no table; it is not a daemon, so the interpreter finishes a
+    landing in flight before it exits.
+
+    Rows travel through a small pinned bounce buffer in asynchronous
+    chunks. A plain .cpu() into pageable memory is a blocking staged copy
+    inside the HIP runtime, and while it runs the ingest thread's own
+    copies and launches queue up behind it: measured, a 218 MB landing
+    held the ingest thread for ~30 ms that way."""
+
+    BOUNCE_WORDS = 1 << 21   # 16 MiB of int64, allocated once, up front
+
+    def __init__(self, device):
+        self.stream = torch.cuda.Stream(device)
+        self._bounce = torch.empty(self.BOUNCE_WORDS, dtype=torch.int64,
+                                   pin_memory=True)
+        self._jobs = deque()
+        self._cv = threading.Condition()
+        self._worker: Optional[threading.Thread] = None
+        self._error: Optional[BaseException] = None
+
+    def fetch(self, src: torch.Tensor) -> "np.ndarray":
+        """Worker thread: device int64 [rows, w] (contiguous) -> u64 numpy
+        in ordinary memory, through the bounce buffer on self.stream."""
+        rows, w = src.shape
+        out = np.empty((rows, w), dtype=np.uint64)
+        step = self.BOUNCE_WORDS // w
+        for r0 in range(0, rows, step):
+            r1 = min(r0 + step, rows)
+            pin = self._bounce[: (r1 - r0) * w].view(r1 - r0, w)
+            pin.copy_(src[r0:r1], non_blocking=True)
+            self.stream.synchronize()
+            np.copyto(out[r0:r1], pin.numpy().view(np.uint64))
+        return out
+
+    def submit(self, table: "RollupTable", event) -> None:
+        with self._cv:
+            self._jobs.append((table, event))
+            if self._worker is None:
+                self._worker = threading.Thread(
+                    target=self._run, name="rollup-drain-lander")
+                self._worker.start()
+
+    def _run(self) -> None:
+        while True:
+            with self._cv:
+                if not self._jobs:
+                    self._worker = None
+                    self._cv.notify_all()
+                    return
+                table, event = self._jobs[0]
+            try:
+                table._land(event, self)
+            except BaseException as e:  # noqa: BLE001 — raised by settle()
+                self._error = e
+            del table, event
+            with self._cv:
+                self._jobs.popleft()
+                self._cv.notify_all()
+
+    def settle(self) -> None:
+        with self._cv:
+            while self._jobs:
+                self._cv.wait()
+            err, self._error = self._error, None
+        if err is not None:
+            raise RuntimeError("rollup drain landing failed") from err
+
+
 class RollupTable:
     def __init__(self, td: TableDef, time_base_s: int, device: str = "cpu",
-                 capacity_pow2: int = 1 << 18):
+                 capacity_pow2: int = 1 << 18,
+                 lander: Optional[_DrainLander] = None):
         assert capacity_pow2 & (capacity_pow2 - 1) == 0
         assert len(td.keys) <= RU_MAX_KEYS - 1
         self.td = td
@@ -202,6 +282,12 @@ class RollupTable:
         # and merge with live groups at read time.
         self.archive: List[tuple] = []  # [(keys u64 [G,nw], vals [G,nv])]
         self.dropped_total = 0
+        # GPU flushes land asynchronously (_DrainLander): the lock guards
+        # archive / dropped_total against the landing thread, _inflight
+        # says this table's staging buffers still hold an unlanded drain
+        self._lock = threading.Lock()
+        self._lander: Optional[_DrainLander] = None
+        self._inflight = False
         if td.derive_from is not None:
             return
         if device == "cpu":
@@ -215,6 +301,18 @@ class RollupTable:
             self.tvals = torch.zeros((capacity_pow2, self.nv),
                                      dtype=torch.int64, device=dev)
             self.drops = torch.zeros(1, dtype=torch.int64, device=dev)
+            # drain staging, allocated here and not at the first flush:
+            # the flush sits on the ingest path and must not allocate.
+            # k_rollup_drain packs the occupied slots into _out_keys /
+            # _out_vals and writes (rows, drops) into _hdr
+            self._out_keys = torch.empty((capacity_pow2, self.nw),
+                                         dtype=torch.int64, device=dev)
+            self._out_vals = torch.empty((capacity_pow2, self.nv),
+                                         dtype=torch.int64, device=dev)
+            self._hdr = torch.zeros(2, dtype=torch.int64, device=dev)
+            self._hdr_host = torch.zeros(2, dtype=torch.int64,
+                                         pin_memory=True)
+            self._lander = lander or _DrainLander(dev)
 
     # RuSpec ABI twin (dfgpu.hip): {u32 interval; u32 n_keys; u8 fam[8];
     # u8 idx[8]; u8 require_nonzero; u8 use_lds} padded to 4-byte alignment
@@ -334,6 +432,7 @@ class RollupTable:
     def _harvest_np(self):
         """(keys u64 [G, nw], vals u64 [G, nv]) of the LIVE table with
         duplicate-slot groups merged — all numpy, no per-row python."""
+        self.settle()
         if self.device == "cpu":
             if not self.table:
                 return (np.zeros((0, self.nw), dtype=np.uint64),
@@ -347,6 +446,7 @@ class RollupTable:
         return raw, vals
 
     def _items(self) -> List[Tuple[tuple, List[int]]]:
+        self.settle()
         if self.device == "cpu":
             return [(k, list(v)) for k, v in self.table.items()]
         mask = self.tkeys != 0
@@ -379,28 +479,79 @@ class RollupTable:
         hash table is already key-unique up to rare duplicate-claim
         slots, which the read-time merge folds) and reset it. Derived
         tables hold no state: they fold from the source's archive +
-        live at read time, so flush skips them entirely — the flush
-        cost is one D2H copy per table, not a host-side merge."""
+        live at read time, so flush skips them entirely.
+
+        CPU: done on return, returns the number of groups archived.
+        GPU: queues one k_rollup_drain on the current stream — behind
+        every update already issued, ahead of every later one — and
+        returns 0 at once; the rows reach the archive on the lander's
+        thread. No host sync here: a flush fires in the middle of ingest,
+        where a blocked host starves the copy queue. Every reader goes
+        through settle()."""
         if self.td.derive_from is not None:
             return 0
-        keys, vals = self._harvest_np()
-        if keys.shape[0]:
-            self.archive.append((keys, vals))
-            if len(self.archive) > 8:
-                # compact: one lexsort merge bounds archive memory and
-                # read-time concat cost (groups recurring across flush
-                # windows collapse)
-                ak = np.concatenate([k for k, _ in self.archive], axis=0)
-                av = np.concatenate([v for _, v in self.archive], axis=0)
-                self.archive = [_np_merge(ak, av, self.ops)]
         if self.device == "cpu":
+            keys, vals = self._harvest_np()
+            if keys.shape[0]:
+                self._archive_chunk(keys, vals)
             self.table.clear()
-        else:
-            self.dropped_total += int(self.drops.item())
-            self.tkeys.zero_()
-            self.tvals.zero_()
-            self.drops.zero_()
-        return keys.shape[0]
+            return keys.shape[0]
+        from ..ops import gpu_ops
+        if self._inflight:
+            # the staging buffers still hold the previous drain: correct
+            # but blocking (not expected at FLUSH_EVERY_ROWS spacing)
+            self.settle()
+        self._hdr.zero_()
+        gpu_ops.rollup_drain(self, self._out_keys, self._out_vals, self._hdr)
+        event = torch.cuda.Event()
+        event.record()
+        self._inflight = True
+        self._lander.submit(self, event)
+        return 0
+
+    def _archive_chunk(self, keys, vals) -> None:
+        with self._lock:
+            self.archive.append((keys, vals))
+            chunks = list(self.archive) if len(self.archive) > 8 else None
+        if chunks is not None:
+            # compact: one lexsort merge bounds archive memory and
+            # read-time concat cost (groups recurring across flush
+            # windows collapse). Appends come from one thread at a time
+            # (the CPU caller or the lander), so the list cannot have
+            # grown in between
+            ak = np.concatenate([k for k, _ in chunks], axis=0)
+            av = np.concatenate([v for _, v in chunks], axis=0)
+            merged = _np_merge(ak, av, self.ops)
+            with self._lock:
+                self.archive = [merged]
+
+    def _land(self, event, lander: _DrainLander) -> None:
+        """Lander thread: wait for the drain, copy its header and then
+        exactly the rows it wrote."""
+        try:
+            event.synchronize()
+            with torch.cuda.stream(lander.stream):
+                self._hdr_host.copy_(self._hdr, non_blocking=True)
+                lander.stream.synchronize()
+                count = int(self._hdr_host[0])
+                drops = int(self._hdr_host[1])
+                if count:
+                    keys = lander.fetch(self._out_keys[:count])
+                    vals = lander.fetch(self._out_vals[:count])
+            if count:
+                self._archive_chunk(keys, vals)
+            with self._lock:
+                self.dropped_total += drops
+        finally:
+            self._inflight = False
+
+    def settle(self) -> None:
+        """Block until every drain queued for this table has landed in
+        the archive (no-op on the CPU and when nothing is queued)."""
+        if self.td.derive_from is not None:
+            self.source_table.settle()
+        elif self._lander is not None:
+            self._lander.settle()
 
     def _fold_np(self, keys, vals):
         """Rebucket key word 0 (relative time) to this table's coarser
@@ -414,7 +565,9 @@ class RollupTable:
         """Merged (keys, vals) across the archive chunks + live."""
         if self.td.derive_from is not None:
             return self._fold_np(*self.source_table._all_groups_np())
-        chunks = self.archive + [self._harvest_np()]
+        live = self._harvest_np()  # settles first
+        with self._lock:
+            chunks = self.archive + [live]
         keys = np.concatenate([k for k, _ in chunks], axis=0)
         vals = np.concatenate([v for _, v in chunks], axis=0)
         return _np_merge(keys, vals, self.ops)
@@ -437,12 +590,14 @@ class RollupTable:
     def drop_count(self) -> int:
         if self.td.derive_from is not None:
             return self.source_table.drop_count()
+        self.settle()
         if self.device == "cpu":
             return self.dropped_total
         return self.dropped_total + int(self.drops.item())
 
     # --------------------------------------------------------- checkpoint
     def state_dict(self):
+        self.settle()
         if self.td.derive_from is not None:
             return {"archive": list(self.archive)}
         if self.device == "cpu":
@@ -454,6 +609,7 @@ class RollupTable:
                 "archive": list(self.archive)}
 
     def load_state_dict(self, st):
+        self.settle()
         self.archive = list(st.get("archive", []))
         if self.td.derive_from is not None:
             return
@@ -474,8 +630,13 @@ class RollupFamily:
 
     def __init__(self, defs: List[TableDef], time_base_s: int,
                  device: str = "cpu"):
+        # one lander (worker + copy stream) for the whole family: its
+        # tables flush together and land one after the other
+        lander = None if device == "cpu" else \
+            _DrainLander(torch.device(device))
         self.tables: Dict[str, RollupTable] = {
-            td.name: RollupTable(td, time_base_s, device, 1 << td.cap_pow2)
+            td.name: RollupTable(td, time_base_s, device, 1 << td.cap_pow2,
+                                 lander=lander)
             for td in defs}
         for t in self.tables.values():
             if t.td.derive_from is not None:
@@ -503,11 +664,17 @@ class RollupFamily:
             self.flush()
 
     def flush(self) -> None:
-        """Interval flush: dump-and-reset every live table (one D2H
-        copy each; derived tables fold at read and carry no state)."""
+        """Interval flush: dump-and-reset every live table (derived
+        tables fold at read and carry no state). On the GPU this only
+        queues the drains; reads settle them."""
         for t in self.tables.values():
             t.flush_live()
         self._rows_since_flush = 0
+
+    def settle(self) -> None:
+        """Block until every queued drain of every table has landed."""
+        for t in self.tables.values():
+            t.settle()
 
     def get(self, name: str) -> Optional[RollupTable]:
         return self.tables.get(name)

@@ -7,7 +7,10 @@ line-oriented or record payloads; OTLP logs arrive via the OTLP route.
 device="cpu" (default): one dict per line on the host; this store is also
 the oracle for the GPU one. device="cuda": store/log_store.py::GpuLogStore
 keeps the payload bytes and the row columns in HBM and answers search() and
-histogram() with HIP kernels (K11).
+histogram() with HIP kernels (K11). Both take an optional regex (K13):
+query/logregex.py validates it identically for either store; the host
+store then matches with Python's `re` on bytes, the GPU store walks the
+compiled DFA in k_log_regex.
 """
 from __future__ import annotations
 
@@ -40,6 +43,14 @@ def norm_needles(substr: Union[str, Sequence[str]]) -> List[str]:
         if not isinstance(s, str):
             raise TypeError("needles are str")
     return [s for s in needles if s]
+
+
+def check_regex(regex, case_insensitive: bool):
+    """search()'s regex argument -> a compiled query.logregex.LogRegex, or
+    None when it constrains nothing. Raises for what either store would
+    refuse; both stores call it before anything else."""
+    from ..query.logregex import check_log_regex
+    return check_log_regex(regex, case_insensitive)
 
 
 def hist_buckets(interval: int, time_start: int, time_end: int) -> int:
@@ -149,7 +160,7 @@ class AppLogPipeline:
 
     # -------------------------------------------------------------- query
     def _matcher(self, substr, severity_max, time_start, time_end,
-                 app_service, case_insensitive):
+                 app_service, case_insensitive, rx=None):
         needles = norm_needles(substr)
         if case_insensitive:
             needles = [fold_ascii(s) for s in needles]
@@ -170,6 +181,9 @@ class AppLogPipeline:
                 for s in needles:
                     if s not in body:
                         return False
+            if rx is not None and not rx.host.search(
+                    r["body"].encode("utf-8", "replace")):
+                return False
             return True
         return match
 
@@ -178,18 +192,34 @@ class AppLogPipeline:
                time_start: Optional[int] = None,
                time_end: Optional[int] = None,
                app_service: Optional[str] = None,
-               case_insensitive: bool = False) -> List[Dict]:
+               case_insensitive: bool = False,
+               regex: Optional[str] = None) -> List[Dict]:
         """Newest-inserted first, cut at `limit`. substr: one needle or up
         to 8, all of which must occur in the body; time_start/time_end are
         inclusive bounds on `time`; app_service is an exact match;
-        case_insensitive folds ASCII A-Z only, on both sides."""
+        case_insensitive folds ASCII A-Z only, on both sides.
+
+        regex: at most one pattern, ANDed with the needles and every other
+        filter; None and "" constrain nothing. A row matches when
+        re.search(regex.encode("utf-8"), body.encode("utf-8", "replace"))
+        does: Python `re` on bytes, so \\d \\w \\s are ASCII, `.` is any
+        byte but \\n, and case_insensitive (re.IGNORECASE) folds A-Z only.
+        The supported subset (query/logregex.py): literals, escapes, `.`,
+        classes, groups, `|`, * + ? {m,n} (lazy or not), ^ or \\A first and
+        $ or \\Z last in the top-level sequence. Backreferences,
+        look-around, \\b, inline flags, anchors elsewhere, patterns over
+        256 bytes and patterns whose DFA exceeds 32 KiB raise ValueError
+        on either store, also on an empty one. Cost on the GPU store: a
+        pattern such as `e.*zzz` walks from every `e` to the end of its
+        row, O(hits x body length); there is no literal prefilter."""
+        rx = check_regex(regex, case_insensitive)
         if self.gpu:
             return self.store.search(
                 substr, severity_max, limit, time_start=time_start,
                 time_end=time_end, app_service=app_service,
-                case_insensitive=case_insensitive)
+                case_insensitive=case_insensitive, regex=regex)
         match = self._matcher(substr, severity_max, time_start, time_end,
-                              app_service, case_insensitive)
+                              app_service, case_insensitive, rx)
         out: List[Dict] = []
         if limit <= 0:
             return out
@@ -204,18 +234,21 @@ class AppLogPipeline:
                   substr: Union[str, Sequence[str]] = "",
                   severity_max: int = 7, *,
                   app_service: Optional[str] = None,
-                  case_insensitive: bool = False) -> List[Dict]:
+                  case_insensitive: bool = False,
+                  regex: Optional[str] = None) -> List[Dict]:
         """Log volume per (time bucket, severity) over [time_start,
         time_end] for the rows search() would match: [{"time":
         bucket_start, "severity": s, "count": c}, ...] sorted by (time,
         severity), nonzero counts only. Severity is clamped to 0..7."""
+        rx = check_regex(regex, case_insensitive)
         n_buckets = hist_buckets(interval, time_start, time_end)
         if self.gpu:
             return self.store.histogram(
                 interval, time_start, time_end, substr, severity_max,
-                app_service=app_service, case_insensitive=case_insensitive)
+                app_service=app_service, case_insensitive=case_insensitive,
+                regex=regex)
         match = self._matcher(substr, severity_max, time_start, time_end,
-                              app_service, case_insensitive)
+                              app_service, case_insensitive, rx)
         counts: Dict[tuple, int] = {}
         if n_buckets:
             for r in self._rows:
@@ -251,19 +284,21 @@ class LogApp:
                         time_end: Optional[int] = None,
                         app_service: Optional[str] = None,
                         case_insensitive: bool = False,
-                        limit: int = 100):
+                        limit: int = 100,
+                        re: Optional[str] = None):
             return guarded(self.pipe.search, q, severity_max, limit,
                            time_start=time_start, time_end=time_end,
                            app_service=app_service,
-                           case_insensitive=case_insensitive)
+                           case_insensitive=case_insensitive, regex=re)
 
         @app.get("/v1/logs/histogram")
         def logs_histogram(interval: int, time_start: int, time_end: int,
                            q: List[str] = Query(default=[]),
                            severity_max: int = 7,
                            app_service: Optional[str] = None,
-                           case_insensitive: bool = False):
+                           case_insensitive: bool = False,
+                           re: Optional[str] = None):
             return guarded(self.pipe.histogram, interval, time_start,
                            time_end, q, severity_max,
                            app_service=app_service,
-                           case_insensitive=case_insensitive)
+                           case_insensitive=case_insensitive, regex=re)

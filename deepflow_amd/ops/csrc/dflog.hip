@@ -20,6 +20,13 @@
 // stages a fixed tile with 16-byte loads, tests every start position from
 // LDS and only maps the (rare) hits back to a row with a binary search over
 // body_off, which is non-decreasing in row index.
+//
+// K13, regex search: k_log_regex is the same flat scan with a DFA walk from
+// every start position in place of the compare. The pattern's tables (up
+// to 32 KiB) are staged in LDS beside the tile: 17168 bytes of static LDS
+// plus the tables as dynamic LDS, 50192 bytes at the most. The largest
+// pattern leaves three workgroups (12 waves) per CU, a small one as many
+// as k_log_scan has; see the kernel.
 #include <string.h>
 #include "dftable.h"
 
@@ -340,11 +347,232 @@ void k_log_select(const int64_t* __restrict__ time,
     }
 }
 
+// ---------------------------------------------------------------- K13
+// Regex search: the flat scan with a DFA walk in place of the compare.
+// The host (query/logregex.py) compiles the pattern to an anchored DFA over
+// byte classes; trying every start position makes it a search. State 0 is
+// dead, state 1 the start; an entry of `next` carries the target state in
+// its low 15 bits and "the target accepts" in bit 15, so a step is one
+// class lookup and one table lookup, both in LDS.
+constexpr uint32_t LOG_RE_OVERHANG = 256;           // tuning, not semantics
+constexpr uint32_t LOG_RE_TABLE_BYTES = 32 * 1024;  // n_states*n_classes*2
+constexpr uint32_t LOG_RE_MAX_PATTERN = 256;
+constexpr uint32_t LOG_RE_MAX_CLASSES = 64;
+constexpr uint32_t LOG_RE_STAGE_CHUNKS = (LOG_TILE + LOG_RE_OVERHANG) / 16;
+// the uploaded tables: class_of u8[256], then next u16[n_states*n_classes]
+constexpr uint32_t LOG_RE_BLOB_CHUNKS = (256 + LOG_RE_TABLE_BYTES) / 16;
+constexpr uint32_t LOG_RE_BIT = 1u << 8;            // needles keep bits 0..7
+constexpr uint32_t RE_ACCEPT = 1u << 15;
+constexpr uint32_t RE_STATE = RE_ACCEPT - 1;
+constexpr uint32_t RE_ANCHOR_START = 1, RE_ANCHOR_END = 2,
+                   RE_END_BEFORE_NL = 4, RE_NULLABLE = 8;
+static_assert(LOG_RE_OVERHANG % 16 == 0, "staged in 16-byte chunks");
+static_assert(LOG_RE_STAGE_CHUNKS * 16 + LOG_RE_BLOB_CHUNKS * 16 + 512 + 16
+              <= 64 * 1024, "static + dynamic LDS of k_log_regex");
+
+// Block b owns match starts in [scan_lo + b*TILE, scan_lo + (b+1)*TILE),
+// clipped at scan_hi, as in k_log_scan, and stages tile + overhang. A match
+// has no length limit: a walk still alive at the end of the staged bytes
+// goes on byte by byte from the pool, up to the end of its row.
+//
+// Bounds. LDS: every tile index is < stage. Global: every pool index is
+// < body_off[r] + body_len[r] <= scan_hi (= the pool's length) for the row
+// r the walk started in; the 16-byte staging loads start below scan_hi and
+// the pool's capacity is a multiple of 16. Nothing reads at or past
+// scan_hi otherwise. Table indices are state * n_classes + class with
+// state < n_states and class < n_classes by construction of the tables
+// (LogRegex asserts it), inside the staged blob.
+//
+// Without anchor_end the shortest accept from a start decides: if it ends
+// past the row's end, no match from that start lies inside the row. With
+// anchor_end the walk runs to the row's end and tests the accept bit there
+// (or one byte earlier when that byte is \n and `$` allows it). With
+// anchor_start only a row's first byte can start a match, so the block
+// walks its rows instead of its positions. A match of length 0 is the
+// host's business (GpuLogStore._flags); empty bodies are skipped here.
+//
+// LDS: 16640 (tile) + 512 (first-step table) + 16 static, and the tables
+// as dynamic LDS sized to the pattern: 256 + n_states * n_classes * 2
+// bytes in 16-byte chunks, 33024 at the most. That is 50192 bytes for the
+// largest pattern, under the 64 KiB a workgroup may have; of the CU's
+// 160 KiB it leaves three workgroups, 12 waves per CU (3 per SIMD). A
+// pattern with tables of a few hundred bytes leaves eight workgroups, the
+// 32 waves a CU holds. The walk is latency-bound on dependent LDS reads,
+// which is what those waves have to hide.
+__global__ __launch_bounds__(BLOCK)
+void k_log_regex(const uint8_t* __restrict__ pool, uint64_t scan_lo,
+                 uint64_t scan_hi,
+                 const int64_t* __restrict__ body_off,
+                 const int32_t* __restrict__ body_len, uint64_t n_rows,
+                 const uint4* __restrict__ blob, uint32_t n_states,
+                 uint32_t nc, uint32_t flags, uint32_t* __restrict__ mask) {
+    __shared__ uint4 s_tile4[LOG_RE_STAGE_CHUNKS];
+    extern __shared__ uint4 s_blob4[];      // blob_chunks of them
+    __shared__ uint16_t s_start[256];       // next[start state] by byte
+    __shared__ int64_t s_rlo, s_rhi;
+
+    const uint32_t tid = threadIdx.x;
+    const uint64_t t0 = scan_lo + (uint64_t)blockIdx.x * LOG_TILE;
+    if (t0 >= scan_hi) return;                        // uniform per block
+    const uint64_t left = scan_hi - t0;
+    const uint32_t n_start = left < LOG_TILE ? (uint32_t)left : LOG_TILE;
+    const uint64_t want = (uint64_t)LOG_TILE + LOG_RE_OVERHANG;
+    const uint32_t stage = left < want ? (uint32_t)left : (uint32_t)want;
+    const uint32_t chunks = (stage + 15) / 16;
+
+    const uint4* src = reinterpret_cast<const uint4*>(pool + t0);
+    for (uint32_t c = tid; c < chunks; c += BLOCK) s_tile4[c] = src[c];
+    const uint32_t blob_chunks = (256 + n_states * nc * 2 + 15) / 16;
+    for (uint32_t c = tid; c < blob_chunks; c += BLOCK) s_blob4[c] = blob[c];
+    if (tid == 0) {
+        // rows that can hold a byte of this tile: [s_rlo, s_rhi]
+        int64_t hi = last_row_le(body_off, 0, (int64_t)n_rows,
+                                 (int64_t)(t0 + n_start - 1));
+        int64_t lo = hi < 0 ? 0
+                   : last_row_le(body_off, 0, hi + 1, (int64_t)t0);
+        s_rlo = lo < 0 ? 0 : lo;
+        s_rhi = hi;
+    }
+    __syncthreads();
+    const int64_t rlo = s_rlo, rhi = s_rhi;
+    if (rhi < 0) return;                              // uniform per block
+
+    const uint32_t* tile32 = reinterpret_cast<const uint32_t*>(s_tile4);
+    const uint8_t* tile8 = reinterpret_cast<const uint8_t*>(s_tile4);
+    const uint8_t* cls = reinterpret_cast<const uint8_t*>(s_blob4);
+    const uint16_t* nxt = reinterpret_cast<const uint16_t*>(s_blob4) + 128;
+    for (uint32_t b = tid; b < 256; b += BLOCK)
+        s_start[b] = nxt[nc + cls[b]];
+    __syncthreads();
+
+    const bool anchor_end = flags & RE_ANCHOR_END;
+    const bool nl_ok = flags & RE_END_BEFORE_NL;
+    const uint32_t nullable = (flags & RE_NULLABLE) ? 1 : 0;
+    const int64_t tile_lo = (int64_t)t0, tile_hi = (int64_t)(t0 + n_start);
+
+    // Both walks take pool offsets g >= t0 and read the bytes below
+    // t0 + stage from LDS, the rest from the pool (two loops, so that
+    // neither load has to be a flat one).
+    const int64_t stage_hi = (int64_t)(t0 + stage);
+    // from state st (not accepting) at pool offset g: is there an accept
+    // whose last byte lies below end?
+    auto shortest = [&](int64_t g, uint32_t st, int64_t end) -> bool {
+        const int64_t lds_end = end < stage_hi ? end : stage_hi;
+        for (; g < lds_end; g++) {
+            uint32_t e = nxt[st * nc + cls[tile8[(uint64_t)g - t0]]];
+            if (!e) return false;
+            if (e & RE_ACCEPT) return true;
+            st = e;
+        }
+        for (; g < end; g++) {
+            uint32_t e = nxt[st * nc + cls[pool[g]]];
+            if (!e) return false;
+            if (e & RE_ACCEPT) return true;
+            st = e;
+        }
+        return false;
+    };
+    // does [p, end) as a whole, or without its final \n, end in an accept?
+    auto to_end = [&](int64_t p, int64_t end) -> bool {
+        uint32_t st = 1, acc = nullable, acc_before = 0;
+        uint8_t last = 0;
+        auto eat = [&](uint8_t b, bool is_last) -> bool {
+            if (is_last) { acc_before = acc; last = b; }
+            uint32_t e = nxt[st * nc + cls[b]];
+            st = e & RE_STATE;
+            acc = e >> 15;
+            return e != 0;
+        };
+        const int64_t lds_end = end < stage_hi ? end : stage_hi;
+        int64_t g = p;
+        bool alive = true;
+        for (; alive && g < lds_end; g++)
+            alive = eat(tile8[(uint64_t)g - t0], g == end - 1);
+        for (; alive && g < end; g++)
+            alive = eat(pool[g], g == end - 1);
+        return acc || (nl_ok && acc_before && last == '\n');
+    };
+    auto mark = [&](int64_t r) {
+        // a stale read only costs a redundant atomic
+        if (!(__atomic_load_n(&mask[r], __ATOMIC_RELAXED) & LOG_RE_BIT))
+            atomicOr(&mask[r], LOG_RE_BIT);
+    };
+
+    if (flags & RE_ANCHOR_START) {
+        // a row is owned by the block its body starts in. Of rows that tie
+        // on body_off all but the last are empty and cannot match.
+        for (int64_t r = rlo + tid; r <= rhi; r += BLOCK) {
+            int64_t p = body_off[r];
+            int64_t end = p + body_len[r];
+            if (p < tile_lo || p >= tile_hi || p >= end) continue;
+            if (anchor_end ? to_end(p, end) : shortest(p, 1, end)) mark(r);
+        }
+        return;
+    }
+
+    // the row of this thread's previous lookup: body [c_lo, c_hi), and
+    // c_next, where the next row's body starts. Between c_hi and c_next lie
+    // header bytes, which belong to no body.
+    int64_t cr = -1, c_lo = 0, c_hi = 0, c_next = 0;
+    auto row_of = [&](int64_t p) -> bool {
+        if (!(cr >= 0 && c_lo <= p && p < c_next)) {
+            int64_t r = last_row_le(body_off, rlo, rhi + 1, p);
+            if (r < 0) return false;
+            cr = r;
+            c_lo = body_off[r];
+            c_hi = c_lo + body_len[r];
+            c_next = (uint64_t)(r + 1) < n_rows ? body_off[r + 1]
+                                                 : INT64_MAX;
+        }
+        return p < c_hi;
+    };
+
+    for (uint32_t it = 0; it * LOG_STRIDE < n_start; it++) {
+        uint32_t q0 = it * LOG_STRIDE + tid * 4;
+        if (q0 >= n_start) continue;
+        uint32_t w = tile32[q0 / 4];
+        for (uint32_t j = 0; j < 4; j++) {
+            uint32_t q = q0 + j;
+            if (q >= n_start) break;
+            // almost every start dies here, on its first byte
+            uint32_t e = s_start[(w >> (8 * j)) & 0xff];
+            if (!e) continue;
+            int64_t p = (int64_t)(t0 + q);
+            if (anchor_end) {
+                if (row_of(p) && to_end(p, c_hi)) mark(cr);
+                continue;
+            }
+            // walk the staged bytes first; the row is looked up only for
+            // a start that got somewhere
+            uint32_t pos = q + 1;
+            while (!(e & RE_ACCEPT) && pos < stage) {
+                e = nxt[e * nc + cls[tile8[pos]]];
+                if (!e) break;
+                pos++;
+            }
+            if (!e || !row_of(p)) continue;
+            if (e & RE_ACCEPT) {
+                if ((int64_t)(t0 + pos) > c_hi) continue;
+            } else if (!shortest((int64_t)(t0 + pos), e, c_hi)) {
+                continue;               // alive at the end of the stage
+            }
+            mark(cr);
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
 
 uint32_t df_log_tile_bytes() { return LOG_TILE; }
+uint32_t df_log_re_overhang() { return LOG_RE_OVERHANG; }
+// out[0..2]: table bytes, pattern bytes, byte classes
+void df_log_re_limits(uint32_t* out) {
+    out[0] = LOG_RE_TABLE_BYTES;
+    out[1] = LOG_RE_MAX_PATTERN;
+    out[2] = LOG_RE_MAX_CLASSES;
+}
 uint64_t df_log_app_seed() { return LOG_APP_SEED; }
 uint32_t df_log_hist_lds_buckets() { return LOG_HIST_LDS_BUCKETS; }
 
@@ -401,6 +629,34 @@ int df_log_scan(const void* pool, uint64_t scan_lo, uint64_t scan_hi,
                        scan_hi, (const int64_t*)body_off,
                        (const int32_t*)body_len, n_rows, nd, fold,
                        (uint32_t*)mask);
+    return (int)hipGetLastError();
+}
+
+// table: device memory, 16-byte aligned and padded to a multiple of 16
+// bytes: class_of u8[256], next u16[n_states * n_classes] (LogRegex.table()).
+// Returns -1 for tables the kernel does not take, and for a pattern that
+// matches the empty string without being anchored at both ends: that one
+// matches every row and is not the kernel's to answer.
+int df_log_regex(const void* pool, uint64_t scan_lo, uint64_t scan_hi,
+                 const void* body_off, const void* body_len, uint64_t n_rows,
+                 const void* table, uint32_t n_states, uint32_t n_classes,
+                 uint32_t flags, void* mask, uint64_t stream) {
+    if (n_classes < 1 || n_classes > LOG_RE_MAX_CLASSES || n_states < 2
+        || n_states > RE_STATE
+        || (uint64_t)n_states * n_classes * 2 > LOG_RE_TABLE_BYTES
+        || (scan_lo & 15) || ((uintptr_t)table & 15))
+        return -1;
+    const uint32_t both = RE_ANCHOR_START | RE_ANCHOR_END;
+    if ((flags & RE_NULLABLE) && (flags & both) != both) return -1;
+    if (n_rows == 0 || scan_hi <= scan_lo) return 0;
+    uint64_t blocks = (scan_hi - scan_lo + LOG_TILE - 1) / LOG_TILE;
+    // dynamic LDS: the tables, in the chunks the kernel stages them in
+    uint32_t lds = (256 + n_states * n_classes * 2 + 15) / 16 * 16;
+    hipLaunchKernelGGL(k_log_regex, dim3((uint32_t)blocks), dim3(BLOCK), lds,
+                       STREAM(stream), (const uint8_t*)pool, scan_lo,
+                       scan_hi, (const int64_t*)body_off,
+                       (const int32_t*)body_len, n_rows, (const uint4*)table,
+                       n_states, n_classes, flags, (uint32_t*)mask);
     return (int)hipGetLastError();
 }
 

@@ -439,6 +439,39 @@ def log_scan(st, needles, fold: bool, mask: torch.Tensor) -> None:
         _stream()), "df_log_scan")
 
 
+LOG_RE_BIT = 1 << 8        # the mask bit k_log_regex sets; needles: 0..7
+
+
+def log_re_limits():
+    """(table bytes, pattern bytes, byte classes) k_log_regex was built
+    for; query/logregex.py carries the same three."""
+    out = (ctypes.c_uint32 * 3)()
+    native.gpu().df_log_re_limits(out)
+    return tuple(int(x) for x in out)
+
+
+def log_regex_table(st, rx) -> torch.Tensor:
+    """rx's tables on st's device, padded to the 16-byte chunks the kernel
+    stages them in."""
+    table = rx.table()
+    blob = np.zeros((table.nbytes + 15) & ~15, dtype=np.uint8)
+    blob[:table.nbytes] = table
+    return torch.from_numpy(blob).to(st.pool.device)
+
+
+def log_regex(st, rx, mask: torch.Tensor,
+              table: torch.Tensor = None) -> None:
+    """OR LOG_RE_BIT into mask[row] for every row whose body holds a
+    non-empty match of rx (a query.logregex.LogRegex). Without `table`
+    (log_regex_table) the tables are uploaded here, once per query."""
+    if table is None:
+        table = log_regex_table(st, rx)
+    native.check(native.gpu().df_log_regex(
+        st.pool.data_ptr(), 0, st.pool_len, st.row_boff.data_ptr(),
+        st.row_blen.data_ptr(), st.n_rows, table.data_ptr(), rx.n_states,
+        rx.n_classes, rx.flags, mask.data_ptr(), _stream()), "df_log_regex")
+
+
 def log_select(st, mask: torch.Tensor, need: int, severity_max: int,
                t_lo: int, t_hi: int, app_key, flags: torch.Tensor,
                hist: torch.Tensor = None, interval: int = 1,

@@ -210,6 +210,14 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_log_scan.restype = ct.c_int
     lib.df_log_scan.argtypes = [p, u64, u64, p, p, u64, ct.c_char_p, p, u32,
                                 u32, p, u64]
+    # K13 regex search over the log pool (k_log_regex in dflog.hip)
+    lib.df_log_re_overhang.restype = u32
+    lib.df_log_re_overhang.argtypes = []
+    lib.df_log_re_limits.restype = None
+    lib.df_log_re_limits.argtypes = [ct.POINTER(u32)]
+    lib.df_log_regex.restype = ct.c_int
+    lib.df_log_regex.argtypes = [p, u64, u64, p, p, u64, p, u32, u32, u32,
+                                 p, u64]
     lib.df_log_select.restype = ct.c_int
     lib.df_log_select.argtypes = [p, p, p, p, u64, u32, i64, i64, u32, u64,
                                   p, u32, u32, p, p, u64, u32, u64]

@@ -1,11 +1,14 @@
-"""GPU-resident application-log store with substring search (K11).
+"""GPU-resident application-log store with substring (K11) and regex
+(K13) search.
 
 The pool is the raw payload: every batch's bytes are appended to a growable
 HBM byte pool unchanged, a HIP kernel parses one line per thread into row
 columns that point back into the pool, and a query is a flat scan of the
 pool (k_log_scan), a per-row filter (k_log_select), one compaction, one
-gather and one D2H copy. The host store in ingest/applog_pipeline.py stays
-the default and is the oracle for this one.
+gather and one D2H copy. A regex is compiled on the host to a DFA
+(query/logregex.py) and walked from every pool position by k_log_regex,
+between the scan and the select. The host store in
+ingest/applog_pipeline.py stays the default and is the oracle for this one.
 
 Host work: per *batch* at ingest (vectorised line split), per *hit* at
 query time. OTLP rows keep their extra keys (trace_id, attr.*, ...) in a
@@ -18,6 +21,14 @@ Known divergences from the host path:
 - non-ASCII digits are not digits;
 - substring search is on bytes, which equals str search for valid UTF-8
   only (needles are at most 128 bytes, at most 8 per query);
+- regex search is Python `re` on the pool's bytes (the host store's
+  body.encode("utf-8", "replace") for valid UTF-8 only, as above) for a
+  subset of its syntax (query/logregex.py lists it): one pattern of at
+  most 256 bytes per query, whose DFA fits 32 KiB; no backreferences,
+  look-around or \\b, and no
+  required-literal prefilter or index, so a pattern such as `e.*zzz` walks
+  from every `e` to the end of its row. The host store refuses exactly the
+  patterns this one refuses;
 - severity is stored as a u8, the pool is limited to 4 GiB, and a row
   whose app name found the app table full reads back with
   app_service "" and app_id -1 (`drops` counts them).
@@ -28,8 +39,8 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ..ingest.applog_pipeline import (fold_ascii, hist_buckets,
-                                      norm_needles)
+from ..ingest.applog_pipeline import (check_regex, fold_ascii,
+                                      hist_buckets, norm_needles)
 from .dictionary import str_hash_py
 
 APP_ID_INVALID = 0xFFFFFFFF
@@ -290,10 +301,12 @@ class GpuLogStore:
 
     def _flags(self, substr, severity_max, time_start, time_end,
                app_service, case_insensitive, hist=None, interval=1,
-               n_buckets=0):
-        """Scan + select -> u8 flag per row (None: nothing can match)."""
+               n_buckets=0, regex=None):
+        """Scan + regex + select -> u8 flag per row (None: nothing can
+        match)."""
         import torch
         from ..ops import gpu_ops
+        rx = check_regex(regex, case_insensitive)
         needles = norm_needles(substr)
         if case_insensitive:
             needles = [fold_ascii(s) for s in needles]
@@ -318,7 +331,16 @@ class GpuLogStore:
         mask = torch.zeros(n, dtype=torch.int32, device=self.device)
         flags = torch.empty(n, dtype=torch.uint8, device=self.device)
         gpu_ops.log_scan(self, needles_b, case_insensitive, mask)
-        gpu_ops.log_select(self, mask, (1 << len(needles_b)) - 1,
+        need = (1 << len(needles_b)) - 1
+        # a pattern that matches the empty string somewhere in every body
+        # constrains nothing; k_log_regex finds non-empty matches only
+        if rx is not None and not rx.matches_everything:
+            need |= gpu_ops.LOG_RE_BIT
+            gpu_ops.log_regex(self, rx, mask)
+            if rx.nullable:             # ^$, ^a*$: the empty bodies too
+                mask |= (self.row_blen[:n] == 0).to(torch.int32) \
+                    * gpu_ops.LOG_RE_BIT
+        gpu_ops.log_select(self, mask, need,
                            min(int(severity_max), 255), t_lo, t_hi, app_key,
                            flags, hist, interval, n_buckets)
         return flags
@@ -328,10 +350,11 @@ class GpuLogStore:
                time_start: Optional[int] = None,
                time_end: Optional[int] = None,
                app_service: Optional[str] = None,
-               case_insensitive: bool = False) -> List[Dict]:
+               case_insensitive: bool = False,
+               regex: Optional[str] = None) -> List[Dict]:
         import torch
         flags = self._flags(substr, severity_max, time_start, time_end,
-                            app_service, case_insensitive)
+                            app_service, case_insensitive, regex=regex)
         if flags is None or limit <= 0:
             return []
         idx = torch.nonzero(flags).reshape(-1)
@@ -400,8 +423,10 @@ class GpuLogStore:
                   substr: Union[str, Sequence[str]] = "",
                   severity_max: int = 7, *,
                   app_service: Optional[str] = None,
-                  case_insensitive: bool = False) -> List[Dict]:
+                  case_insensitive: bool = False,
+                  regex: Optional[str] = None) -> List[Dict]:
         import torch
+        check_regex(regex, case_insensitive)
         n_buckets = hist_buckets(interval, time_start, time_end)
         if n_buckets == 0:
             norm_needles(substr)
@@ -410,7 +435,8 @@ class GpuLogStore:
                            device=self.device)
         flags = self._flags(substr, severity_max, time_start, time_end,
                             app_service, case_insensitive, hist=hist,
-                            interval=int(interval), n_buckets=n_buckets)
+                            interval=int(interval), n_buckets=n_buckets,
+                            regex=regex)
         if flags is None:
             return []
         cells = torch.nonzero(hist).reshape(-1)

@@ -11,6 +11,11 @@ histogram() with HIP kernels (K11). Both take an optional regex (K13):
 query/logregex.py validates it identically for either store; the host
 store then matches with Python's `re` on bytes, the GPU store walks the
 compiled DFA in k_log_regex.
+
+Retention: both stores drop oldest-inserted rows, by hand (evict_rows,
+evict_before) or past max_rows; the GPU store also bounds its pool in bytes
+and compacts itself on the device (k_log_evict). The host store stays the
+exact oracle: fed the same calls, both hold the same rows.
 """
 from __future__ import annotations
 
@@ -65,18 +70,51 @@ def hist_buckets(interval: int, time_start: int, time_end: int) -> int:
     return n
 
 
+def check_retention(max_rows, keep_fraction) -> None:
+    if max_rows is not None and max_rows < 1:
+        raise ValueError("max_rows must be >= 1")
+    if not 0 < keep_fraction <= 1:
+        raise ValueError("keep_fraction must be in (0, 1]")
+
+
+def rows_to_evict(n_rows: int, max_rows, keep_fraction: float) -> int:
+    """The row rule, applied by either store after a batch is appended:
+    past max_rows, the oldest rows go until max(1, floor(max_rows *
+    keep_fraction)) are left."""
+    if max_rows is None or n_rows <= max_rows:
+        return 0
+    return n_rows - max(1, int(max_rows * keep_fraction))
+
+
+def _body_bytes(r: Dict) -> int:
+    return len(str(r.get("body", "")).encode("utf-8", "replace"))
+
+
 class AppLogPipeline:
+    """max_rows / keep_fraction: retention by row count, identical on both
+    stores (rows_to_evict); both None-default limits mean an unbounded
+    store. Other keywords go to the GPU store (store/log_store.py), which
+    alone knows max_pool_bytes."""
+
     def __init__(self, counter: Optional[Counter] = None,
-                 device: str = "cpu", **store_kw):
+                 device: str = "cpu", *, max_rows: Optional[int] = None,
+                 keep_fraction: float = 0.5, **store_kw):
         self.device = device
         self.gpu = not str(device).startswith("cpu")
         self._rows: List[Dict] = []
-        # SmartEncoding for repetitive fields
+        # SmartEncoding for repetitive fields; never shrunk, so an app
+        # whose rows were all evicted keeps its id
         self.app_interner: Dict[str, int] = {}
         self.counter = counter or Counter("ingester.app_log")
+        check_retention(max_rows, keep_fraction)
+        self.max_rows = max_rows
+        self.keep_fraction = keep_fraction
+        self._evicted_rows = 0
+        self._evictions = 0
         if self.gpu:
             from ..store.log_store import GpuLogStore
-            self.store = GpuLogStore(device=device, **store_kw)
+            self.store = GpuLogStore(device=device, max_rows=max_rows,
+                                     keep_fraction=keep_fraction, **store_kw)
         elif store_kw:
             raise TypeError(f"unexpected arguments for the host store: "
                             f"{sorted(store_kw)}")
@@ -98,6 +136,74 @@ class AppLogPipeline:
     def n_rows(self) -> int:
         return self.store.n_rows if self.gpu else len(self._rows)
 
+    # ---------------------------------------------------------- retention
+    @property
+    def evicted_rows(self) -> int:
+        return self.store.evicted_rows if self.gpu else self._evicted_rows
+
+    @property
+    def evictions(self) -> int:
+        return self.store.evictions if self.gpu else self._evictions
+
+    def _host_evict(self, n: int) -> int:
+        n = min(int(n), len(self._rows))
+        if n <= 0:
+            return 0
+        del self._rows[:n]
+        self._evicted_rows += n
+        self._evictions += 1
+        return n
+
+    def _counted(self, fn, *args):
+        """Run a store call that may evict; what it evicted goes to the
+        counter as logs_evicted."""
+        before = self.evicted_rows
+        try:
+            return fn(*args)
+        finally:
+            gone = self.evicted_rows - before
+            if gone:
+                self.counter.add("logs_evicted", gone)
+
+    def evict_rows(self, n: int) -> int:
+        """Drop the min(n, n_rows) oldest-inserted rows; -> how many went
+        (n <= 0: none). Apps keep their ids."""
+        return self._counted(
+            self.store.evict_rows if self.gpu else self._host_evict, n)
+
+    def evict_before(self, t: int) -> int:
+        """Drop the longest insertion-order prefix in which every row has
+        time < t: rows are in arrival order, not time order, and the cut
+        is the first row with time >= t even when older rows follow it."""
+        if self.gpu:
+            return self._counted(self.store.evict_before, t)
+        first = next((i for i, r in enumerate(self._rows)
+                      if r["time"] >= t), len(self._rows))
+        return self._counted(self._host_evict, first)
+
+    def _host_row_rule(self) -> None:
+        self._host_evict(rows_to_evict(len(self._rows), self.max_rows,
+                                       self.keep_fraction))
+
+    def stats(self) -> Dict:
+        """Rows, retention counters, stored bytes (GPU store: row columns
+        plus pool; host store: UTF-8 bytes of the bodies, counted per call)
+        and the limits."""
+        out = {
+            "rows": self.n_rows,
+            "evicted_rows": self.evicted_rows,
+            "evictions": self.evictions,
+            "stored_bytes": self.store.stored_bytes() if self.gpu
+            else sum(_body_bytes(r) for r in self._rows),
+            "max_rows": self.max_rows,
+            "max_pool_bytes": self.store.max_pool_bytes if self.gpu
+            else None,
+            "keep_fraction": self.keep_fraction,
+        }
+        if self.gpu:
+            out["pool_bytes"] = self.store.pool_len
+        return out
+
     def _intern(self, s: str) -> int:
         i = self.app_interner.get(s)
         if i is None:
@@ -112,9 +218,10 @@ class AppLogPipeline:
         fallback for free-form lines, which get the time `now` (None: the
         wall clock)."""
         if self.gpu:
-            n = self.store.ingest_lines(
-                payload, agent_id=agent_id, log_type=log_type,
-                now=int(time.time()) if now is None else now)
+            n = self._counted(
+                lambda: self.store.ingest_lines(
+                    payload, agent_id=agent_id, log_type=log_type,
+                    now=int(time.time()) if now is None else now))
             self.counter.add("logs_in", n)
             return n
         n = 0
@@ -143,12 +250,13 @@ class AppLogPipeline:
             })
             n += 1
         self.counter.add("logs_in", n)
+        self._counted(self._host_row_rule)
         return n
 
     def ingest_rows(self, rows: List[Dict]) -> int:
         """Append pre-converted rows (OTLP logs path)."""
         if self.gpu:
-            n = self.store.ingest_rows(rows)
+            n = self._counted(self.store.ingest_rows, rows)
             self.counter.add("logs_in", n)
             return n
         for r in rows:
@@ -156,6 +264,7 @@ class AppLogPipeline:
             r.setdefault("app_id", self._intern(app))
             self._rows.append(r)
         self.counter.add("logs_in", len(rows))
+        self._counted(self._host_row_rule)
         return len(rows)
 
     # -------------------------------------------------------------- query
@@ -290,6 +399,10 @@ class LogApp:
                            time_start=time_start, time_end=time_end,
                            app_service=app_service,
                            case_insensitive=case_insensitive, regex=re)
+
+        @app.get("/v1/logs/stats")
+        def logs_stats():
+            return self.pipe.stats()
 
         @app.get("/v1/logs/histogram")
         def logs_histogram(interval: int, time_start: int, time_end: int,

@@ -561,6 +561,124 @@ void k_log_regex(const uint8_t* __restrict__ pool, uint64_t scan_lo,
     }
 }
 
+// ---------------------------------------------------------- retention
+// Evicting the `first` oldest rows is a prefix cut, out of place: the row
+// columns lose their first `first` entries and the pool loses the bytes
+// below
+//     cut = (body_off[first-1] + body_len[first-1]) & ~15,
+// the end of the last evicted body rounded down to 16 (the whole pool when
+// every row goes). The new pool is [arena | old bytes cut..pool_len).
+//
+// Why nothing a kept row needs lies below cut. k_log_ingest places row i's
+// body at [off + b_at, off + len): it always runs to the end of the line,
+// for parsed lines, free-form lines and the pre_* layout alike, and the
+// header and the app token lie inside the line before it. Lines of a batch
+// do not overlap and come in increasing offset (split_log_lines yields
+// them sorted, _ingest_row_run lays them end to end), and a batch starts
+// at the pool's length, past every earlier line. So the line of row
+// `first` starts at or after the end of body first-1 >= cut, and so does
+// everything of every later row.
+//
+// What does lie below cut and is still needed: app names. A slot records
+// where its *claimer's* token lies (app_off), and the claimer may be
+// evicted while later rows keep the id. Every live slot (tkeys != 0) whose
+// app_off < cut has its name copied into the arena at the front of the new
+// pool; names that an earlier eviction put into an arena lie below cut and
+// move again. A slot with app_off >= cut keeps pointing into the copied
+// suffix, whoever claimed it (the rounding can leave the last evicted
+// row's token above cut; its bytes are copied with the suffix), and is
+// rebased like a body: new = old - cut + arena. Tokens of distinct slots
+// are disjoint byte ranges that start below cut and end before cut + 16
+// (a token ends before its body does), so the packed arena, padded to 16,
+// is at most cut + 16 and the new pool at most 16 bytes longer than the
+// old one; the wrapper sizes the new pool from the arena it read back.
+//
+// Arena bytes sit below body_off[0]: last_row_le gives -1 there, so the
+// scans attribute a hit inside a relocated name to no row, as they do for
+// header bytes. body_off stays non-decreasing (one constant is added).
+//
+// tkeys, app_len and drops are not touched: app ids are slot indices.
+
+// pass 1, thread per app slot: bump-allocate arena bytes. reloc[s] = new
+// offset of the slot's name, or -1 for a slot that is empty or stays in the
+// suffix. out[0] (zeroed on the stream before the launch) ends as the
+// packed arena length, out[1] is the cut, so the host learns both from one
+// copy. Every thread derives the cut from the same two words.
+__global__ __launch_bounds__(BLOCK)
+void k_log_evict_plan(const uint64_t* __restrict__ tkeys,
+                      const int64_t* __restrict__ app_off,
+                      const int32_t* __restrict__ app_len, uint32_t cap,
+                      const int64_t* __restrict__ body_off,
+                      const int32_t* __restrict__ body_len, uint64_t first,
+                      uint64_t n_rows, int64_t pool_len,
+                      int64_t* __restrict__ reloc,
+                      unsigned long long* __restrict__ out) {
+    const int64_t cut = first == n_rows ? pool_len
+        : (body_off[first - 1] + body_len[first - 1]) & ~(int64_t)15;
+    if (blockIdx.x == 0 && threadIdx.x == 0)
+        out[1] = (unsigned long long)cut;
+    const uint32_t step = gridDim.x * BLOCK;
+    for (uint32_t s = blockIdx.x * BLOCK + threadIdx.x; s < cap; s += step) {
+        int64_t to = -1;
+        if (tkeys[s] != EMPTY_KEY && app_off[s] < cut)
+            to = (int64_t)atomicAdd(&out[0],
+                                    (unsigned long long)(uint32_t)app_len[s]);
+        reloc[s] = to;
+    }
+}
+
+// pass 2, one flat grid-stride index space: [0, cap) are app slots (copy a
+// relocated name and point the slot at it, or rebase the slot), [cap,
+// cap + n_keep) are kept rows (new_col[r] = old_col[r + first]). Names are
+// tokens of a line, tens of bytes: a byte loop per thread, as in
+// k_log_ingest. app_off is updated in place; each slot is read and written
+// by one thread only.
+//
+// Bounds. A name is read from [off, off + len) of the old pool only when
+// that lies inside [0, old_len), and written to [to, to + len) of the new pool
+// only when that lies inside [0, arena); pass 1 hands out disjoint ranges
+// that sum to *arena_len <= arena. Row r reads old_col[r + first] with
+// r + first < first + n_keep = the old row count.
+__global__ __launch_bounds__(BLOCK)
+void k_log_evict(const uint8_t* __restrict__ old_pool,
+                 uint8_t* __restrict__ new_pool, int64_t old_len,
+                 int64_t cut, int64_t arena,
+                 const uint64_t* __restrict__ tkeys,
+                 int64_t* __restrict__ app_off,
+                 const int32_t* __restrict__ app_len,
+                 const int64_t* __restrict__ reloc, uint32_t cap,
+                 LogRows src, LogRows dst, uint64_t first, uint64_t n_keep) {
+    const int64_t shift = arena - cut;
+    const uint64_t total = (uint64_t)cap + n_keep;
+    const uint64_t step = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < total;
+         i += step) {
+        if (i < cap) {
+            if (tkeys[i] == EMPTY_KEY) continue;
+            const int64_t to = reloc[i];
+            const int64_t off = app_off[i];
+            if (to < 0) {
+                app_off[i] = off + shift;
+                continue;
+            }
+            const int64_t len = (int64_t)(uint32_t)app_len[i];
+            if (off >= 0 && off + len <= old_len && to + len <= arena)
+                for (int64_t b = 0; b < len; b++)
+                    new_pool[to + b] = old_pool[off + b];
+            app_off[i] = to;
+        } else {
+            const uint64_t r = i - cap, o = r + first;
+            dst.time[r] = src.time[o];
+            dst.severity[r] = src.severity[o];
+            dst.agent_id[r] = src.agent_id[o];
+            dst.log_type[r] = src.log_type[o];
+            dst.app_id[r] = src.app_id[o];
+            dst.body_off[r] = src.body_off[o] + shift;
+            dst.body_len[r] = src.body_len[o];
+        }
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -678,6 +796,70 @@ int df_log_select(const void* time, const void* severity,
                        t_hi, use_app, app_key, (const uint64_t*)tkeys,
                        app_cap, need, (uint8_t*)flags,
                        (unsigned long long*)hist, interval, n_buckets);
+    return (int)hipGetLastError();
+}
+
+// Retention, pass 1, for dropping the `first` oldest of n_rows rows:
+// reloc[cap] (i64) and out[2] (u64, device; out[0] is zeroed here on the
+// stream) = {packed arena length, cut}. The caller reads out back, pads
+// the arena to 16 and allocates the new pool before pass 2.
+int df_log_evict_plan(const void* tkeys, uint32_t cap, const void* app_off,
+                      const void* app_len, const void* row_boff,
+                      const void* row_blen, uint64_t first, uint64_t n_rows,
+                      uint64_t pool_len, void* reloc, void* out,
+                      uint64_t stream) {
+    if (cap == 0 || first == 0 || first > n_rows
+        || pool_len >= (1ull << 62))
+        return -1;
+    hipError_t e = hipMemsetAsync(out, 0, sizeof(unsigned long long),
+                                  STREAM(stream));
+    if (e != hipSuccess) return (int)e;
+    uint32_t blocks = grid_for(cap);
+    if (blocks > LOG_SELECT_MAX_BLOCKS) blocks = LOG_SELECT_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_log_evict_plan, dim3(blocks), dim3(BLOCK), 0,
+                       STREAM(stream), (const uint64_t*)tkeys,
+                       (const int64_t*)app_off, (const int32_t*)app_len, cap,
+                       (const int64_t*)row_boff, (const int32_t*)row_blen,
+                       first, n_rows, (int64_t)pool_len, (int64_t*)reloc,
+                       (unsigned long long*)out);
+    return (int)hipGetLastError();
+}
+
+// Retention, pass 2: names into new_pool[0, arena), app_off in place, the
+// seven row columns from row `first` on into new_* (n_keep rows). The
+// suffix old_pool[cut, old_len) -> new_pool[arena, ...) is a plain copy and
+// the caller's. Returns -1 for a cut or an arena that is not the shape the
+// kernels were written for.
+int df_log_evict(const void* old_pool, void* new_pool, uint64_t old_len,
+                 uint64_t cut, uint64_t arena, uint64_t new_cap,
+                 const void* tkeys, uint32_t cap, void* app_off,
+                 const void* app_len, const void* reloc,
+                 const void* row_time, const void* row_sev,
+                 const void* row_agent, const void* row_type,
+                 const void* row_app, const void* row_boff,
+                 const void* row_blen,
+                 void* new_time, void* new_sev, void* new_agent,
+                 void* new_type, void* new_app, void* new_boff,
+                 void* new_blen, uint64_t first, uint64_t n_keep,
+                 uint64_t stream) {
+    if (cap == 0 || first == 0 || cut > old_len || (arena & 15)
+        || (n_keep && (cut & 15)) || arena + (old_len - cut) > new_cap
+        || old_len >= (1ull << 62))
+        return -1;
+    LogRows src{(int64_t*)row_time, (uint8_t*)row_sev, (uint32_t*)row_agent,
+                (uint16_t*)row_type, (uint32_t*)row_app, (int64_t*)row_boff,
+                (int32_t*)row_blen};
+    LogRows dst{(int64_t*)new_time, (uint8_t*)new_sev, (uint32_t*)new_agent,
+                (uint16_t*)new_type, (uint32_t*)new_app, (int64_t*)new_boff,
+                (int32_t*)new_blen};
+    uint32_t blocks = grid_for((uint64_t)cap + n_keep);
+    if (blocks > LOG_SELECT_MAX_BLOCKS) blocks = LOG_SELECT_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_log_evict, dim3(blocks), dim3(BLOCK), 0,
+                       STREAM(stream), (const uint8_t*)old_pool,
+                       (uint8_t*)new_pool, (int64_t)old_len, (int64_t)cut,
+                       (int64_t)arena, (const uint64_t*)tkeys,
+                       (int64_t*)app_off, (const int32_t*)app_len,
+                       (const int64_t*)reloc, cap, src, dst, first, n_keep);
     return (int)hipGetLastError();
 }
 

@@ -484,3 +484,56 @@ def log_select(st, mask: torch.Tensor, need: int, severity_max: int,
         st.tkeys.data_ptr(), st.tkeys.numel(), need, flags.data_ptr(),
         hist.data_ptr() if hist is not None else 0, interval, n_buckets,
         _stream()), "df_log_select")
+
+
+def log_evict(st, first: int):
+    """Drop the `first` oldest rows of st (0 < first <= st.n_rows) by
+    compacting it out of place into fresh row columns and a fresh pool
+    (k_log_evict_plan, k_log_evict, one D2D copy of the pool's suffix; the
+    layout is described in dflog.hip). One host read: the arena length and
+    the cut. Replaces st's pool, row columns, pool_len and n_rows and
+    rewrites app_off; tkeys, app_len and drops stay. What the host keys by
+    row index (OTLP extras, dense app ids) is the caller's to fix.
+    -> (cut, arena): bytes dropped from the front of the old pool, bytes of
+    relocated app names at the front of the new one."""
+    n = st.n_rows
+    if not 0 < first <= n:
+        raise ValueError("first must be in 1..n_rows")
+    lib = native.gpu()
+    dev = st.pool.device
+    cap = st.tkeys.numel()
+    reloc = torch.empty(cap, dtype=torch.int64, device=dev)
+    out = torch.empty(2, dtype=torch.int64, device=dev)
+    native.check(lib.df_log_evict_plan(
+        st.tkeys.data_ptr(), cap, st.app_off.data_ptr(),
+        st.app_len.data_ptr(), st.row_boff.data_ptr(),
+        st.row_blen.data_ptr(), first, n, st.pool_len, reloc.data_ptr(),
+        out.data_ptr(), _stream()), "df_log_evict_plan")
+    packed, cut = out.tolist()
+    arena = (packed + 15) & ~15
+    assert 0 <= cut <= st.pool_len
+    keep = n - first
+    tail = st.pool_len - cut
+    new_len = arena + tail
+    # the arena can outgrow the cut by 16 bytes at the most (dflog.hip)
+    new_cap = max(st.pool.numel(), (new_len + 15) & ~15)
+    pool = torch.empty(new_cap, dtype=torch.uint8, device=dev)
+    assert pool.data_ptr() % 16 == 0
+    pool[:arena].zero_()
+    old_cols = [getattr(st, name) for name, _ in st._COLS]
+    new_cols = [torch.empty_like(c) for c in old_cols]
+    native.check(lib.df_log_evict(
+        st.pool.data_ptr(), pool.data_ptr(), st.pool_len, cut, arena,
+        new_cap, st.tkeys.data_ptr(), cap, st.app_off.data_ptr(),
+        st.app_len.data_ptr(), reloc.data_ptr(),
+        *[c.data_ptr() for c in old_cols],
+        *[c.data_ptr() for c in new_cols], first, keep, _stream()),
+        "df_log_evict")
+    if tail:
+        pool[arena:new_len] = st.pool[cut:st.pool_len]
+    for (name, _), c in zip(st._COLS, new_cols):
+        setattr(st, name, c)
+    st.pool = pool
+    st.pool_len = new_len
+    st.n_rows = keep
+    return cut, arena

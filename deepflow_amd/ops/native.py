@@ -221,6 +221,14 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_log_select.restype = ct.c_int
     lib.df_log_select.argtypes = [p, p, p, p, u64, u32, i64, i64, u32, u64,
                                   p, u32, u32, p, p, u64, u32, u64]
+    # retention for the log store (k_log_evict_plan, k_log_evict)
+    lib.df_log_evict_plan.restype = ct.c_int
+    lib.df_log_evict_plan.argtypes = [p, u32, p, p, p, p, u64, u64, u64, p,
+                                      p, u64]
+    lib.df_log_evict.restype = ct.c_int
+    lib.df_log_evict.argtypes = [p, p, u64, u64, u64, u64, p, u32, p, p, p,
+                                 p, p, p, p, p, p, p,
+                                 p, p, p, p, p, p, p, u64, u64, u64]
 
 
 def gpu() -> ct.CDLL:

@@ -33,7 +33,10 @@ class DeepflowServer:
                  native_pump: bool = False,
                  pump_port: int = 0,
                  gpu_profiles: bool = False,
-                 gpu_logs: bool = False):
+                 gpu_logs: bool = False,
+                 log_max_rows: Optional[int] = None,
+                 log_max_pool_bytes: Optional[int] = None,
+                 log_retain_s: Optional[float] = None):
         self.device = device
         self.kg = KnowledgeGraphTable(device=device)
         if platform_cfg is not None:
@@ -116,20 +119,31 @@ class DeepflowServer:
         self.events = EventPipeline()
         # gpu_logs: keep application logs in HBM and search them with
         # HIP kernels (store/log_store.py); off by default
+        # Retention: log_max_rows bounds either store by rows,
+        # log_max_pool_bytes the GPU store's pool by bytes, log_retain_s
+        # drops rows older than that many seconds (checked from the ingest
+        # handlers, at most once per second; no thread of its own).
+        if log_retain_s is not None and log_retain_s <= 0:
+            raise ValueError("log_retain_s must be > 0")
+        self.log_retain_s = log_retain_s
+        self._log_retain_at = 0.0
         if gpu_logs and not str(device).startswith("cpu"):
-            self.applogs = AppLogPipeline(device=device)
+            store_kw = {} if log_max_pool_bytes is None else \
+                {"max_pool_bytes": log_max_pool_bytes}
+            self.applogs = AppLogPipeline(device=device,
+                                          max_rows=log_max_rows, **store_kw)
+        elif log_max_pool_bytes is not None:
+            raise ValueError("log_max_pool_bytes needs the GPU log store "
+                             "(gpu_logs=True on a GPU device)")
         else:
-            self.applogs = AppLogPipeline()
+            self.applogs = AppLogPipeline(max_rows=log_max_rows)
         self.receiver.register(framing.MSG_PROC_EVENT,
                                lambda hdr, payload:
                                self.events.ingest_proc_events(
                                    payload.tobytes()))
         for mt in (framing.MSG_APPLICATION_LOG, framing.MSG_SYSLOG,
                    framing.MSG_AGENT_LOG):
-            self.receiver.register(
-                mt, lambda hdr, payload:
-                self.applogs.ingest_lines(payload.tobytes(),
-                                          agent_id=hdr.agent_id))
+            self.receiver.register(mt, self._on_log)
         from .control import ControllerLite
         self.controller = ControllerLite(
             kg=self.kg, event_sink=self.events.add_resource_event)
@@ -187,7 +201,12 @@ class DeepflowServer:
         @self.app.get("/v1/debug/store")
         def debug_store():
             segs = self.l7.segments
+            logs = {"log_rows": self.applogs.n_rows,
+                    "log_evicted_rows": self.applogs.evicted_rows}
+            if self.applogs.gpu:
+                logs["log_pool_bytes"] = self.applogs.store.pool_len
             return {
+                **logs,
                 "l7_rows": segs.n_rows,
                 "l7_segments": len(segs.segments),
                 "l7_alloc_bytes": segs.total_alloc_bytes(),
@@ -288,6 +307,7 @@ class DeepflowServer:
             except Exception:
                 return {"error": "bad LogsData"}
             self.applogs.ingest_rows(rows)
+            self._log_retain()
             return {"accepted": len(rows)}
 
         @self.app.post("/otlp/v1/metrics")
@@ -480,6 +500,24 @@ class DeepflowServer:
         with self._lock:
             pipe.ingest(payload, offs, lens)
 
+    def _on_log(self, hdr, payload):
+        n = self.applogs.ingest_lines(payload.tobytes(),
+                                      agent_id=hdr.agent_id)
+        self._log_retain()
+        return n
+
+    def _log_retain(self) -> None:
+        """log_retain_s: drop the leading rows older than the window, at
+        most once per second of wall clock."""
+        if self.log_retain_s is None:
+            return
+        import time
+        now = time.time()
+        if now - self._log_retain_at < 1.0:
+            return
+        self._log_retain_at = now
+        self.applogs.evict_before(int(now - self.log_retain_s))
+
     def _on_otel(self, hdr, payload) -> None:
         """OTLP frames carry one zlib-compressed TracesData blob
         (reference decoder.go:235-266); convert to AppProtoLogsData and run
@@ -611,9 +649,23 @@ def main() -> None:
                     help="load on start, save every --checkpoint-interval "
                          "seconds and on shutdown")
     ap.add_argument("--checkpoint-interval", type=float, default=300.0)
+    ap.add_argument("--gpu-logs", action="store_true",
+                    help="keep application logs in HBM (GPU device only)")
+    ap.add_argument("--log-max-rows", type=int, default=None,
+                    help="application-log retention by rows")
+    ap.add_argument("--log-max-pool-bytes", type=int, default=None,
+                    help="application-log retention by pool bytes "
+                         "(needs --gpu-logs)")
+    ap.add_argument("--log-retain-s", type=float, default=None,
+                    help="drop application logs older than this many "
+                         "seconds")
     args = ap.parse_args()
     device = args.device or ("cuda" if torch.cuda.is_available() else "cpu")
-    srv = DeepflowServer(device=device, tcp_port=args.tcp_port)
+    srv = DeepflowServer(device=device, tcp_port=args.tcp_port,
+                         gpu_logs=args.gpu_logs,
+                         log_max_rows=args.log_max_rows,
+                         log_max_pool_bytes=args.log_max_pool_bytes,
+                         log_retain_s=args.log_retain_s)
     if args.checkpoint_dir:
         restored = srv.enable_checkpoints(args.checkpoint_dir,
                                           args.checkpoint_interval)

@@ -31,7 +31,24 @@ Known divergences from the host path:
   patterns this one refuses;
 - severity is stored as a u8, the pool is limited to 4 GiB, and a row
   whose app name found the app table full reads back with
-  app_service "" and app_id -1 (`drops` counts them).
+  app_service "" and app_id -1 (`drops` counts them);
+- retention by bytes exists here only. max_pool_bytes bounds pool_len (the
+  payload bytes as they arrived, headers and line breaks included, plus
+  the names of apps whose first row is gone), not the bodies: before a
+  batch of nb bytes is appended and would pass the limit, the oldest rows
+  go until pool_len <= min(floor(max_pool_bytes * keep_fraction),
+  max_pool_bytes - nb). The cut falls on a row boundary rounded down to 16
+  bytes and the room is judged with an upper bound for the names, so a few
+  more rows than strictly needed may go. A batch larger than the limit is
+  a ValueError; ingest_rows makes room per run of equal (agent_id,
+  log_type), so such a run fails after the runs before it were stored.
+
+Retention (evict_rows, evict_before, max_rows, as on the host store, and
+max_pool_bytes) drops oldest-inserted rows by compacting the store on the
+device into a fresh pool and fresh columns (k_log_evict in dflog.hip).
+Apps are never dropped; the name of an app whose claiming row is gone moves
+to an arena at the front of the new pool, below the first body, where the
+scans attribute bytes to no row.
 """
 from __future__ import annotations
 
@@ -39,8 +56,9 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import numpy as np
 
-from ..ingest.applog_pipeline import (check_regex, fold_ascii,
-                                      hist_buckets, norm_needles)
+from ..ingest.applog_pipeline import (check_regex, check_retention,
+                                      fold_ascii, hist_buckets,
+                                      norm_needles, rows_to_evict)
 from .dictionary import str_hash_py
 
 APP_ID_INVALID = 0xFFFFFFFF
@@ -97,10 +115,25 @@ class GpuLogStore:
     """Row columns + app dictionary + raw payload pool in HBM."""
 
     def __init__(self, device: str = "cuda", row_capacity: int = 1 << 16,
-                 pool_capacity: int = 1 << 22, app_capacity: int = 1 << 12):
+                 pool_capacity: int = 1 << 22, app_capacity: int = 1 << 12,
+                 max_rows: Optional[int] = None,
+                 max_pool_bytes: Optional[int] = None,
+                 keep_fraction: float = 0.5):
         import torch
         if app_capacity < 1 or app_capacity & (app_capacity - 1):
             raise ValueError("app_capacity must be a power of two")
+        check_retention(max_rows, keep_fraction)
+        if max_pool_bytes is not None:
+            if max_pool_bytes < 1:
+                raise ValueError("max_pool_bytes must be >= 1")
+            if max_pool_bytes > POOL_LIMIT:
+                raise ValueError("max_pool_bytes is at most 4 GiB")
+            pool_capacity = min(pool_capacity, max_pool_bytes)
+        self.max_rows = max_rows
+        self.max_pool_bytes = max_pool_bytes
+        self.keep_fraction = keep_fraction
+        self.evicted_rows = 0
+        self.evictions = 0
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise ValueError("GpuLogStore needs a GPU device")
@@ -165,6 +198,10 @@ class GpuLogStore:
             return
         while cap < need:
             cap *= 2
+        if self.max_pool_bytes is not None:
+            # _make_room saw to it that need <= max_pool_bytes
+            cap = min(cap, _pad16(self.max_pool_bytes))
+            assert need <= cap
         if cap > POOL_LIMIT:
             raise MemoryError("log pool would exceed 4 GiB")
         pool = torch.zeros(cap, dtype=torch.uint8, device=self.device)
@@ -185,14 +222,19 @@ class GpuLogStore:
     # ------------------------------------------------------------- ingest
     def _ingest(self, buf: np.ndarray, line_off: np.ndarray,
                 line_len: np.ndarray, now: int, agent_id: int,
-                log_type: str, pre=None) -> int:
+                log_type: str, pre=None, extras=None) -> int:
         """One H2D copy, one D2D append of the payload to the pool, one
-        k_log_ingest launch."""
+        k_log_ingest launch. With max_pool_bytes set, room is made first
+        (_make_room). extras: {line index: extra keys}, recorded under the
+        row indices the lines get."""
         import torch
         from ..ops import gpu_ops
         n_lines = int(line_off.shape[0])
         if n_lines == 0:
             return 0
+        self._make_room(int(buf.shape[0]))
+        for k, extra in (extras or {}).items():
+            self._extras[self.n_rows + k] = extra
         parts = [line_off, line_len, buf]
         if pre is not None:
             parts += list(pre)
@@ -230,8 +272,9 @@ class GpuLogStore:
                      log_type: str = "system", now: int = 0) -> int:
         buf = np.frombuffer(bytes(payload), dtype=np.uint8)
         line_off, line_len = split_log_lines(buf)
-        return self._ingest(buf, line_off, line_len, now, agent_id,
-                            log_type)
+        n = self._ingest(buf, line_off, line_len, now, agent_id, log_type)
+        self._apply_row_rule()
+        return n
 
     def ingest_rows(self, rows: List[Dict]) -> int:
         """Pre-parsed rows (OTLP). Rows are grouped into runs of equal
@@ -248,6 +291,7 @@ class GpuLogStore:
                 j += 1
             n += self._ingest_row_run(rows[i:j], key[0], key[1])
             i = j
+        self._apply_row_rule()
         return n
 
     def _ingest_row_run(self, rows: List[Dict], agent_id: int,
@@ -258,6 +302,7 @@ class GpuLogStore:
         line_len = np.zeros(m, dtype=np.int32)
         times = np.zeros(m, dtype=np.int64)
         sevs = np.zeros(m, dtype=np.uint8)
+        extras: Dict[int, Dict] = {}
         for k, r in enumerate(rows):
             app = str(r.get("app_service", "")).encode("utf-8", "replace")
             body = str(r["body"]).encode("utf-8", "replace")
@@ -269,12 +314,90 @@ class GpuLogStore:
             sevs[k] = min(max(int(r["severity"]), 0), 255)
             extra = {key: v for key, v in r.items() if key not in CORE_KEYS}
             if extra:
-                self._extras[self.n_rows + k] = extra
+                extras[k] = extra
         line_off = np.zeros(m, dtype=np.int64)
         np.cumsum(line_len[:-1], out=line_off[1:])
         buf = np.frombuffer(b"".join(chunks), dtype=np.uint8)
         return self._ingest(buf, line_off, line_len, 0, agent_id, log_type,
-                            pre=(app_len, times, sevs))
+                            pre=(app_len, times, sevs), extras=extras)
+
+    # ---------------------------------------------------------- retention
+    def evict_rows(self, n: int) -> int:
+        """Drop the min(n, n_rows) oldest-inserted rows; -> how many went.
+        A device-side compaction into a fresh pool and fresh row columns
+        (gpu_ops.log_evict): peak memory is old pool plus new pool. Apps are
+        never forgotten: an app whose rows are all gone keeps its slot, its
+        name (moved to the front of the new pool) and its app_id."""
+        from ..ops import gpu_ops
+        first = min(int(n), self.n_rows)
+        if first <= 0:
+            return 0
+        # dense ids are first-seen order over *all* rows ever stored: bring
+        # them up to date while the rows are still there
+        self._dense_ids()
+        gpu_ops.log_evict(self, first)
+        self._extras = {r - first: e for r, e in self._extras.items()
+                        if r >= first}
+        self._dense_rows = self.n_rows
+        self.evicted_rows += first
+        self.evictions += 1
+        return first
+
+    def evict_before(self, t: int) -> int:
+        """Drop the longest insertion-order prefix in which every row has
+        time < t (times are not monotone in row index: the cut is the first
+        row with time >= t, wherever older rows lie after it). The index is
+        found on the device; one scalar goes to the host."""
+        import torch
+        n = self.n_rows
+        if n == 0:
+            return 0
+        lim = (1 << 63) - 1
+        t = max(-lim - 1, min(lim, int(t)))
+        idx = torch.arange(n, device=self.device)
+        first = torch.where(self.row_time[:n] >= t, idx,
+                            torch.full_like(idx, n)).min()
+        return self.evict_rows(int(first.item()))
+
+    def _apply_row_rule(self) -> None:
+        self.evict_rows(rows_to_evict(self.n_rows, self.max_rows,
+                                      self.keep_fraction))
+
+    def _make_room(self, nb: int) -> None:
+        """The byte rule, before a batch of nb bytes is appended: when the
+        pool would pass max_pool_bytes, evict the fewest oldest rows that
+        bring pool_len down to min(floor(max_pool_bytes * keep_fraction),
+        max_pool_bytes - nb). `first` is chosen on the device (one scalar
+        to the host) from the non-decreasing cuts the rows would give, with
+        the padded sum of all live app names as an upper bound for the
+        arena; when no row set meets the target, everything goes."""
+        import torch
+        limit = self.max_pool_bytes
+        if limit is None:
+            return
+        if nb > limit:
+            raise ValueError(f"a batch of {nb} bytes does not fit "
+                             f"max_pool_bytes={limit}")
+        if self.pool_len + nb <= limit:
+            return
+        n = self.n_rows
+        if n:
+            target = min(int(limit * self.keep_fraction), limit - nb)
+            live = self.tkeys != 0
+            arena = (torch.sum(self.app_len.to(torch.int64) * live) + 15) \
+                & ~15
+            # new pool_len = arena + pool_len - cut(first) <= target
+            need = arena + (self.pool_len - target)
+            cuts = (self.row_boff[:n] + self.row_blen[:n]) & ~15
+            # lines end in increasing order, so cuts is sorted; the last row
+            # stands for "everything": its cut is the whole pool
+            cuts[n - 1] = self.pool_len
+            first = torch.clamp(torch.searchsorted(cuts, need.reshape(1)),
+                                max=n - 1) + 1
+            self.evict_rows(int(first.item()))
+        if self.pool_len + nb > limit:
+            raise MemoryError("the app names alone leave no room for the "
+                              "batch under max_pool_bytes")
 
     # -------------------------------------------------------------- query
     def _dense_ids(self) -> Dict[int, int]:

@@ -10,7 +10,9 @@ keeps the payload bytes and the row columns in HBM and answers search() and
 histogram() with HIP kernels (K11). Both take an optional regex (K13):
 query/logregex.py validates it identically for either store; the host
 store then matches with Python's `re` on bytes, the GPU store walks the
-compiled DFA in k_log_regex.
+compiled DFA in k_log_regex. patterns() (K14) groups the matching rows by
+the template of their body (query/logpattern.py, one definition for both
+stores); the GPU store hashes the templates in k_log_patterns.
 
 Retention: both stores drop oldest-inserted rows, by hand (evict_rows,
 evict_before) or past max_rows; the GPU store also bounds its pool in bytes
@@ -369,6 +371,66 @@ class AppLogPipeline:
         return [{"time": t, "severity": s, "count": c}
                 for (t, s), c in sorted(counts.items())]
 
+    def patterns(self, substr: Union[str, Sequence[str]] = "",
+                 severity_max: int = 7, limit: int = 20, *,
+                 time_start: Optional[int] = None,
+                 time_end: Optional[int] = None,
+                 app_service: Optional[str] = None,
+                 case_insensitive: bool = False,
+                 regex: Optional[str] = None,
+                 max_patterns: int = 1 << 16) -> Dict:
+        """The rows search() would match, grouped by the template of their
+        body (query/logpattern.py: tokens that hold a digit become `<*>`,
+        over the first 512 bytes of the body as UTF-8). The filters mean
+        what they mean for search(); case_insensitive touches them only,
+        never the template. ->
+
+            {"matched": rows that passed the filters,
+             "distinct": patterns found,
+             "dropped_rows": matched rows whose pattern found the table full,
+             "patterns": [{"pattern": text, "count": n, "sample": row}, ...]}
+
+        `patterns` is sorted by count, largest first, ties by the oldest
+        first occurrence, and cut at `limit`. `sample` is the
+        newest-inserted matching row of the pattern, as search() returns
+        it. max_patterns, a power of two, is the size of the GPU store's
+        query-scoped table: a pattern that finds it full loses all of its
+        rows to dropped_rows, every reported count stays exact. The host
+        store validates it and never drops."""
+        from ..query.logpattern import (check_max_patterns, render,
+                                        template_symbols)
+        rx = check_regex(regex, case_insensitive)
+        check_max_patterns(max_patterns)
+        if self.gpu:
+            return self.store.patterns(
+                substr, severity_max, limit, time_start=time_start,
+                time_end=time_end, app_service=app_service,
+                case_insensitive=case_insensitive, regex=regex,
+                max_patterns=max_patterns)
+        match = self._matcher(substr, severity_max, time_start, time_end,
+                              app_service, case_insensitive, rx)
+        # symbols -> [count, first row index, newest row]; by the symbol
+        # tuple, not the rendered text: a body may hold a literal "<*>"
+        groups: Dict[tuple, list] = {}
+        matched = 0
+        for i, r in enumerate(self._rows):
+            if not match(r):
+                continue
+            matched += 1
+            sym = template_symbols(r["body"].encode("utf-8", "replace"))
+            g = groups.get(sym)
+            if g is None:
+                groups[sym] = [1, i, r]
+            else:
+                g[0] += 1
+                g[2] = r
+        top = sorted(groups.items(), key=lambda kv: (-kv[1][0], kv[1][1]))
+        return {"matched": matched, "distinct": len(groups),
+                "dropped_rows": 0,
+                "patterns": [{"pattern": render(sym), "count": g[0],
+                              "sample": g[2]}
+                             for sym, g in top[:max(int(limit), 0)]]}
+
 
 class LogApp:
     """HTTP surface: log search and the log-volume histogram. Works on
@@ -399,6 +461,22 @@ class LogApp:
                            time_start=time_start, time_end=time_end,
                            app_service=app_service,
                            case_insensitive=case_insensitive, regex=re)
+
+        @app.get("/v1/logs/patterns")
+        def logs_patterns(q: List[str] = Query(default=[]),
+                          severity_max: int = 7,
+                          time_start: Optional[int] = None,
+                          time_end: Optional[int] = None,
+                          app_service: Optional[str] = None,
+                          case_insensitive: bool = False,
+                          limit: int = 20,
+                          re: Optional[str] = None,
+                          max_patterns: int = 1 << 16):
+            return guarded(self.pipe.patterns, q, severity_max, limit,
+                           time_start=time_start, time_end=time_end,
+                           app_service=app_service,
+                           case_insensitive=case_insensitive, regex=re,
+                           max_patterns=max_patterns)
 
         @app.get("/v1/logs/stats")
         def logs_stats():

@@ -27,6 +27,10 @@
 // plus the tables as dynamic LDS, 50192 bytes at the most. The largest
 // pattern leaves three workgroups (12 waves) per CU, a small one as many
 // as k_log_scan has; see the kernel.
+//
+// K14, log patterns: k_log_patterns hashes the template of every selected
+// body (one lane per row) and groups the rows in a query-scoped table, with
+// a per-block LDS table in front of it; see the kernel.
 #include <string.h>
 #include "dftable.h"
 
@@ -679,6 +683,179 @@ void k_log_evict(const uint8_t* __restrict__ old_pool,
     }
 }
 
+// ---------------------------------------------------------------- K14
+// Log patterns: group the selected rows by the template of their body.
+// query/logpattern.py is the definition; this is its one-pass form. A body
+// is cut into tokens at delimiter bytes, a token that holds an ASCII digit
+// collapses to one WILDCARD symbol, and the key is FNV-1a over the symbols
+// (bytes 0..255, WILDCARD, TRUNC), finished with mix64. `saved` is h as it
+// stood after the last delimiter, so a token that turns out to hold a digit
+// is taken back with one assignment.
+//
+// Row scan, not flat scan: unlike a substring match, the key depends on
+// where the body starts, and every selected body is read exactly once. One
+// lane per row; adjacent lanes' rows are adjacent in the pool, so a wave's
+// loads fall into one contiguous region of a few KiB, and the prefix cap
+// bounds the divergence on length.
+constexpr uint32_t LOG_PAT_PREFIX = 512;
+constexpr uint32_t LOG_PAT_WILDCARD = 0x100, LOG_PAT_TRUNC = 0x101;
+constexpr uint64_t LOG_PAT_FNV_OFFSET = 0xCBF29CE484222325ull;
+constexpr uint64_t LOG_PAT_FNV_PRIME = 0x100000001B3ull;
+// per-block pre-aggregation table: 5 KiB of LDS
+constexpr uint32_t LOG_PAT_LSLOT = 256;
+constexpr uint32_t LOG_PAT_LPROBE = 8;
+
+// one bit per byte base..base+63: every byte <= 0x20 and "'(),;:=[]{}|
+constexpr uint64_t pat_delim_bits(uint32_t base) {
+    const char set[] = "\"'(),;:=[]{}|";
+    uint64_t m = 0;
+    for (uint32_t i = 0; i < 64; i++) {
+        uint32_t c = base + i;
+        bool d = c <= 0x20;
+        for (uint32_t k = 0; k + 1 < sizeof(set); k++)
+            d = d || c == (uint8_t)set[k];
+        if (d) m |= 1ull << i;
+    }
+    return m;
+}
+constexpr uint64_t LOG_PAT_DELIM_LO = pat_delim_bits(0);
+constexpr uint64_t LOG_PAT_DELIM_HI = pat_delim_bits(64);
+
+DEV bool pat_is_delim(uint32_t c) {         // bytes >= 0x80 are literals
+    return c < 128
+        && (((c < 64 ? LOG_PAT_DELIM_LO : LOG_PAT_DELIM_HI) >> (c & 63)) & 1);
+}
+
+DEV uint64_t pat_fold(uint64_t h, uint32_t sym) {
+    return (h ^ sym) * LOG_PAT_FNV_PRIME;
+}
+
+// Key of the body at pool[off, off + len). The bytes come in aligned
+// 16-byte chunks; of each chunk only the bytes inside the body's prefix are
+// looked at.
+// Bounds: a chunk starts at a multiple of 16 below off + n <= pool_len <=
+// the pool's capacity, which is a multiple of 16 (as the pool's base is),
+// so the chunk ends inside the capacity. A row that does not lie inside
+// [0, pool_len) is read as far as pool_len and no further.
+DEV uint64_t pattern_key(const uint8_t* __restrict__ pool, uint64_t pool_len,
+                         int64_t body_off, int32_t body_len) {
+    uint64_t h = LOG_PAT_FNV_OFFSET, saved = h;
+    bool digit = false;
+    const uint64_t off = body_off < 0 ? pool_len : (uint64_t)body_off;
+    const uint32_t len = body_len < 0 ? 0 : (uint32_t)body_len;
+    uint64_t end = off + (len < LOG_PAT_PREFIX ? len : LOG_PAT_PREFIX);
+    if (end > pool_len) end = pool_len;
+    for (uint64_t a = off & ~15ull; a < end; a += 16) {
+        const uint4 v = *reinterpret_cast<const uint4*>(pool + a);
+        const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+        const uint32_t lo = a < off ? (uint32_t)(off - a) : 0;
+        const uint32_t hi = end - a < 16 ? (uint32_t)(end - a) : 16;
+#pragma unroll
+        for (uint32_t b = 0; b < 16; b++) {
+            if (b < lo || b >= hi) continue;
+            const uint32_t c = (w[b / 4] >> (8 * (b % 4))) & 0xffu;
+            if (pat_is_delim(c)) {
+                if (digit) h = pat_fold(saved, LOG_PAT_WILDCARD);
+                digit = false;
+                h = pat_fold(h, c);
+                saved = h;
+            } else {
+                h = pat_fold(h, c);
+                digit = digit || (c >= '0' && c <= '9');
+            }
+        }
+    }
+    if (digit) h = pat_fold(saved, LOG_PAT_WILDCARD);
+    if (len > LOG_PAT_PREFIX) h = pat_fold(h, LOG_PAT_TRUNC);
+    h = mix64(h);
+    return h ? h : 1ull;                    // never EMPTY_KEY
+}
+
+// query-scoped table: slot = pattern. count is zeroed, first_row is
+// ROW_NONE and last_row 0 before the launch (last_row means something only
+// where count != 0).
+struct PatTable {
+    uint64_t* keys;              // [cap]
+    unsigned long long* count;   // [cap]
+    uint32_t* first_row;         // [cap] atomicMin
+    uint32_t* last_row;          // [cap] atomicMax
+    unsigned long long* drops;   // rows whose pattern found the table full
+    uint32_t cap_mask;
+};
+
+// The table only fills: a key that once found it full finds it full ever
+// after, and a key that holds a slot is found by every later probe. So a
+// pattern either gets all of its rows counted or all of them dropped.
+DEV void pat_add_global(const PatTable& pt, uint64_t key, uint32_t n,
+                        uint32_t rmin, uint32_t rmax) {
+    uint32_t slot = table_claim(pt.keys, pt.cap_mask, key,
+                                (uint32_t)(mix64(key) & pt.cap_mask));
+    if (slot == ROW_NONE) {
+        atomicAdd(pt.drops, (unsigned long long)n);
+        return;
+    }
+    atomicAdd(&pt.count[slot], (unsigned long long)n);
+    atomicMin(&pt.first_row[slot], rmin);
+    atomicMax(&pt.last_row[slot], rmax);
+}
+
+// thread per row (grid-stride). A handful of patterns usually carry most
+// rows: counts, lowest and highest row are merged per block in an LDS table
+// and flushed once per block, as the edges of k_trace_fold are. A row whose
+// key finds no LDS slot within LOG_PAT_LPROBE steps goes to the global
+// table directly; sums, minima and maxima do not care which way a row took.
+// out_key (optional, u64 per row): the key of every selected row.
+__global__ __launch_bounds__(BLOCK)
+void k_log_patterns(const uint8_t* __restrict__ pool, uint64_t pool_len,
+                    const int64_t* __restrict__ body_off,
+                    const int32_t* __restrict__ body_len,
+                    const uint8_t* __restrict__ flags, uint64_t n_rows,
+                    PatTable pt, uint64_t* __restrict__ out_key) {
+    __shared__ unsigned long long lkey[LOG_PAT_LSLOT];
+    __shared__ uint32_t lcnt[LOG_PAT_LSLOT];
+    __shared__ uint32_t lmin[LOG_PAT_LSLOT];
+    __shared__ uint32_t lmax[LOG_PAT_LSLOT];
+    for (uint32_t i = threadIdx.x; i < LOG_PAT_LSLOT; i += BLOCK) {
+        lkey[i] = EMPTY_KEY;
+        lcnt[i] = 0;
+        lmin[i] = ROW_NONE;
+        lmax[i] = 0;
+    }
+    __syncthreads();
+    const uint64_t step = (uint64_t)gridDim.x * BLOCK;
+    for (uint64_t r = (uint64_t)blockIdx.x * BLOCK + threadIdx.x;
+         r < n_rows; r += step) {
+        if (!flags[r]) continue;
+        const uint64_t key = pattern_key(pool, pool_len, body_off[r],
+                                         body_len[r]);
+        if (out_key) out_key[r] = key;
+        const uint32_t row = (uint32_t)r;       // n_rows < ROW_NONE
+        uint32_t ls = (uint32_t)(mix64(key) & (LOG_PAT_LSLOT - 1));
+        bool placed = false;
+        for (uint32_t probe = 0; probe < LOG_PAT_LPROBE && !placed; probe++) {
+            unsigned long long cur = lkey[ls];
+            if (cur == EMPTY_KEY)
+                cur = atomicCAS(&lkey[ls], EMPTY_KEY,
+                                (unsigned long long)key);
+            if (cur == EMPTY_KEY || cur == key) placed = true;
+            else ls = (ls + 1) & (LOG_PAT_LSLOT - 1);
+        }
+        if (placed) {
+            atomicAdd(&lcnt[ls], 1u);
+            atomicMin(&lmin[ls], row);
+            atomicMax(&lmax[ls], row);
+        } else {
+            pat_add_global(pt, key, 1, row, row);
+        }
+    }
+    __syncthreads();
+    for (uint32_t i = threadIdx.x; i < LOG_PAT_LSLOT; i += BLOCK) {
+        unsigned long long key = lkey[i];
+        if (key != EMPTY_KEY)
+            pat_add_global(pt, key, lcnt[i], lmin[i], lmax[i]);
+    }
+}
+
 }  // namespace
 
 extern "C" {
@@ -860,6 +1037,37 @@ int df_log_evict(const void* old_pool, void* new_pool, uint64_t old_len,
                        (int64_t)arena, (const uint64_t*)tkeys,
                        (int64_t*)app_off, (const int32_t*)app_len,
                        (const int64_t*)reloc, cap, src, dst, first, n_keep);
+    return (int)hipGetLastError();
+}
+
+uint32_t df_log_pattern_prefix() { return LOG_PAT_PREFIX; }
+uint32_t df_log_pattern_lds_slots() { return LOG_PAT_LSLOT; }
+
+// K14: fold the rows with flags[r] != 0 into the pattern table (device
+// memory, `cap` slots, a power of two: keys u64 and count u64 zeroed,
+// first_row u32 = ROW_NONE, last_row u32 = 0, drops one zeroed u64).
+// out_key: nullptr, or u64[n_rows] that gets the key of every flagged row.
+// Returns -1 for a table, a pool or a row count the kernel does not take.
+int df_log_patterns(const void* pool, uint64_t pool_len,
+                    const void* body_off, const void* body_len,
+                    const void* flags, uint64_t n_rows, void* keys,
+                    uint32_t cap, void* count, void* first_row,
+                    void* last_row, void* drops, void* out_key,
+                    uint64_t stream) {
+    if (cap == 0 || (cap & (cap - 1)) || ((uintptr_t)pool & 15)
+        || n_rows >= ROW_NONE)
+        return -1;
+    if (n_rows == 0) return 0;
+    PatTable pt{(uint64_t*)keys, (unsigned long long*)count,
+                (uint32_t*)first_row, (uint32_t*)last_row,
+                (unsigned long long*)drops, cap - 1};
+    uint32_t blocks = grid_for(n_rows);
+    if (blocks > LOG_SELECT_MAX_BLOCKS) blocks = LOG_SELECT_MAX_BLOCKS;
+    hipLaunchKernelGGL(k_log_patterns, dim3(blocks), dim3(BLOCK), 0,
+                       STREAM(stream), (const uint8_t*)pool, pool_len,
+                       (const int64_t*)body_off, (const int32_t*)body_len,
+                       (const uint8_t*)flags, n_rows, pt,
+                       (uint64_t*)out_key);
     return (int)hipGetLastError();
 }
 

@@ -486,6 +486,53 @@ def log_select(st, mask: torch.Tensor, need: int, severity_max: int,
         _stream()), "df_log_select")
 
 
+class LogPatternTable:
+    """Query-scoped table of k_log_patterns: slot = pattern."""
+
+    def __init__(self, device, cap: int):
+        self.cap = cap
+        self.keys = torch.zeros(cap, dtype=torch.int64, device=device)
+        self.count = torch.zeros(cap, dtype=torch.int64, device=device)
+        # u32 words: ROW_NONE until a row takes them with atomicMin
+        self.first_row = torch.full((cap,), -1, dtype=torch.int32,
+                                    device=device)
+        # atomicMax; valid where count != 0
+        self.last_row = torch.zeros(cap, dtype=torch.int32, device=device)
+        self.drops = torch.zeros(1, dtype=torch.int64, device=device)
+
+    def reset(self) -> None:
+        self.keys.zero_()
+        self.count.zero_()
+        self.first_row.fill_(-1)
+        self.last_row.zero_()
+        self.drops.zero_()
+
+
+def log_patterns(st, flags: torch.Tensor, cap: int,
+                 out_key: torch.Tensor = None,
+                 table: LogPatternTable = None) -> LogPatternTable:
+    """Group the rows of st with flags[row] != 0 (u8 per row) by the
+    template of their body (query/logpattern.py) into a table of `cap`
+    slots, a power of two: a fresh one, or `table` (reset by the caller).
+    One launch; nothing comes to the host.
+    out_key (i64 per row, tests): gets the key of every flagged row."""
+    n = st.n_rows
+    assert flags.dtype == torch.uint8 and flags.numel() >= n
+    assert out_key is None or \
+        (out_key.dtype == torch.int64 and out_key.numel() >= n)
+    # the kernel loads aligned 16-byte chunks that start below pool_len
+    assert st.pool_len <= st.pool.numel() and st.pool.numel() % 16 == 0
+    t = table if table is not None else LogPatternTable(st.pool.device, cap)
+    assert t.cap == cap
+    native.check(native.gpu().df_log_patterns(
+        st.pool.data_ptr(), st.pool_len, st.row_boff.data_ptr(),
+        st.row_blen.data_ptr(), flags.data_ptr(), n, t.keys.data_ptr(), cap,
+        t.count.data_ptr(), t.first_row.data_ptr(), t.last_row.data_ptr(),
+        t.drops.data_ptr(), out_key.data_ptr() if out_key is not None else 0,
+        _stream()), "df_log_patterns")
+    return t
+
+
 def log_evict(st, first: int):
     """Drop the `first` oldest rows of st (0 < first <= st.n_rows) by
     compacting it out of place into fresh row columns and a fresh pool

@@ -229,6 +229,14 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_log_evict.argtypes = [p, p, u64, u64, u64, u64, p, u32, p, p, p,
                                  p, p, p, p, p, p, p,
                                  p, p, p, p, p, p, p, u64, u64, u64]
+    # K14 log patterns (k_log_patterns in dflog.hip)
+    lib.df_log_pattern_prefix.restype = u32
+    lib.df_log_pattern_prefix.argtypes = []
+    lib.df_log_pattern_lds_slots.restype = u32
+    lib.df_log_pattern_lds_slots.argtypes = []
+    lib.df_log_patterns.restype = ct.c_int
+    lib.df_log_patterns.argtypes = [p, u64, p, p, p, u64, p, u32, p, p, p, p,
+                                    p, u64]
 
 
 def gpu() -> ct.CDLL:

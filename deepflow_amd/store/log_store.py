@@ -7,7 +7,9 @@ columns that point back into the pool, and a query is a flat scan of the
 pool (k_log_scan), a per-row filter (k_log_select), one compaction, one
 gather and one D2H copy. A regex is compiled on the host to a DFA
 (query/logregex.py) and walked from every pool position by k_log_regex,
-between the scan and the select. The host store in
+between the scan and the select. patterns() (K14) groups the selected rows
+by the template of their body with one more kernel, k_log_patterns, and
+brings only the top groups' newest rows to the host. The host store in
 ingest/applog_pipeline.py stays the default and is the oracle for this one.
 
 Host work: per *batch* at ingest (vectorised line split), per *hit* at
@@ -29,6 +31,16 @@ Known divergences from the host path:
   required-literal prefilter or index, so a pattern such as `e.*zzz` walks
   from every `e` to the end of its row. The host store refuses exactly the
   patterns this one refuses;
+- patterns() (K14, query/logpattern.py) takes the template from the pool's
+  bytes, not from a str: equal to the host store's
+  body.encode("utf-8", "replace") for valid UTF-8 only. Only the first 512
+  bytes of a body count on either store. Patterns are told apart by a
+  64-bit key here and by the symbol tuple on the host: two templates with
+  one key would be counted as one. The query-scoped table has max_patterns
+  slots (a power of two, default 65536); a pattern that finds it full
+  loses all of its rows to dropped_rows, which the host store never does,
+  and has probed every slot to find that out, so the table is to be sized
+  above the number of patterns expected;
 - severity is stored as a u8, the pool is limited to 4 GiB, and a row
   whose app name found the app table full reads back with
   app_service "" and app_id -1 (`drops` counts them);
@@ -567,6 +579,51 @@ class GpuLogStore:
         return [{"time": int(time_start) + (cell // 8) * int(interval),
                  "severity": cell % 8, "count": cnt}
                 for cell, cnt in zip(host[0].tolist(), host[1].tolist())]
+
+    def patterns(self, substr: Union[str, Sequence[str]] = "",
+                 severity_max: int = 7, limit: int = 20, *,
+                 time_start: Optional[int] = None,
+                 time_end: Optional[int] = None,
+                 app_service: Optional[str] = None,
+                 case_insensitive: bool = False,
+                 regex: Optional[str] = None,
+                 max_patterns: int = 1 << 16) -> Dict:
+        """AppLogPipeline.patterns on this store: the flags of search(), one
+        k_log_patterns launch into a query-scoped table of max_patterns
+        slots, the top `limit` slots chosen on the device, their newest
+        rows hydrated. Three scalars and `limit` rows come to the host."""
+        import torch
+        from ..ops import gpu_ops
+        from ..query.logpattern import (check_max_patterns, render,
+                                        template_symbols)
+        check_regex(regex, case_insensitive)
+        check_max_patterns(max_patterns)
+        flags = self._flags(substr, severity_max, time_start, time_end,
+                            app_service, case_insensitive, regex=regex)
+        if flags is None:
+            return {"matched": 0, "distinct": 0, "dropped_rows": 0,
+                    "patterns": []}
+        t = gpu_ops.log_patterns(self, flags, max_patterns)
+        slots = torch.nonzero(t.count).reshape(-1)
+        distinct = int(slots.numel())
+        cnt = t.count[slots]
+        first = t.first_row[slots].to(torch.int64) & 0xFFFFFFFF
+        # count descending, ties by the lowest first row: two stable sorts.
+        # A row has one pattern, so first rows are distinct and the order
+        # does not depend on which slot a pattern landed in.
+        order = torch.argsort(first, stable=True)
+        order = order[torch.argsort(cnt[order], descending=True,
+                                    stable=True)]
+        top = order[:min(max(int(limit), 0), distinct)]
+        last = t.last_row[slots[top]].to(torch.int64) & 0xFFFFFFFF
+        host = torch.cat([flags.sum(dtype=torch.int64).reshape(1), t.drops,
+                          cnt[top]]).cpu().tolist()
+        out = []
+        for n, row in zip(host[2:], self._hydrate(last)):
+            sym = template_symbols(row["body"].encode("utf-8", "replace"))
+            out.append({"pattern": render(sym), "count": n, "sample": row})
+        return {"matched": host[0], "distinct": distinct,
+                "dropped_rows": host[1], "patterns": out}
 
     # ------------------------------------------------------- introspection
     @property

@@ -1563,6 +1563,143 @@ __global__ void k_query_agg(SegView s, QuerySpec q, uint32_t n, uint64_t base_ro
     agg_lds_flush(q, lkey, lgslot, lrows, lagg, gvals, cnt_a, overflow);
 }
 
+// ---- K15: exact distinct counts per group (Uniq / UniqExact) ----
+// A second pass over the rows k_query_agg saw, into the same group table:
+// guniq[slot][u] lines up with gvals[slot] because the group hash below is
+// agg_row_lds's, bit for bit. What is counted is the number of distinct
+// (group, value tuple) PAIRS, each identified by a 64-bit hash that is
+// claimed once in a query-scoped table `pkeys` (dftable.h rules):
+//
+//   h    = the group hash of agg_row_lds (seed 0x243F6A8885A308D3,
+//          h = mix64(h ^ key_k ^ (k << 56)) per key, 0 -> 1)
+//   vh   = UNIQ_SEED ^ ((u + 1) * 0x9E3779B97F4A7C15)       for item u
+//   vh   = mix64(vh ^ value_j ^ (j << 56))                  for each arg j
+//   pair = mix64(h ^ vh), 0 -> 1
+//
+// (host twin: query/spec.py UNIQ_SEED; tests/uniq_cases.py pair_hash).
+// value_j is src_value() of the argument with bucket 0. The thread whose
+// CAS claims the pair adds 1 to its group's counter; everybody else who
+// meets the pair, in this launch or a later one on the same tables, adds
+// nothing. Two different pairs with one 64-bit hash count once.
+#define QMAX_UNIQ 4
+#define QMAX_UNIQ_ARGS 4
+
+struct QUniqCol { uint8_t family; uint16_t idx; };
+struct QUniq { QUniqCol cols[QMAX_UNIQ_ARGS]; uint32_t n_args; };
+struct UniqSpec { QUniq items[QMAX_UNIQ]; uint32_t n_uniq; };
+
+constexpr uint64_t UNIQ_SEED = 0x13198A2E03707344ull;
+constexpr uint64_t UNIQ_ITEM_MUL = 0x9E3779B97F4A7C15ull;
+// Block-local filter of recently seen pairs: direct-mapped, 4096 x 8 B =
+// 32 KB of LDS. The index is bits 32..43 of the pair hash: the pair table
+// starts its probe at the low bits of mix64(pair) and the group tables use
+// the low bits of h, so these bits are spent nowhere else.
+constexpr uint32_t UNIQ_FILTER_SLOTS = 4096;
+constexpr uint32_t UNIQ_FILTER_SHIFT = 32;
+// Fewer, longer-lived workgroups than k_query_agg: a filter slot pays off
+// only when its block meets the pair again, and 4 blocks x 32 KB still fit
+// a CU's LDS.
+constexpr uint32_t UNIQ_MAX_BLOCKS = 1024;
+
+// One atomicAdd per (wave, counter) instead of one per lane. With few
+// groups every claimed pair lands on the same guniq word, and 4M adds to one
+// address were the whole kernel (48 ms against 0.1 ms for k_query_agg,
+// the rate of one contended L2 word). Each round the lanes here that
+// share the first lane's counter index elect their lowest lane, which adds
+// their number; a round retires at least one lane, so 64 rounds retire
+// every lane of the wave. Which lanes the compiler keeps together at this
+// point only decides how much is merged: every lane is counted once,
+// either in its cohort's popcount or by the add of its own below.
+DEV void uniq_count_add(unsigned long long* guniq, uint32_t idx) {
+    for (uint32_t r = 0; r < 64; r++) {
+        uint32_t first = __builtin_amdgcn_readfirstlane(idx);
+        // the vote is taken by every lane still in the loop, on the
+        // predicate itself: a ballot of `true` inside the branch came back
+        // with lanes of other counters in it
+        bool mine = idx == first;
+        unsigned long long peers = __ballot(mine);
+        if (mine) {
+            if ((threadIdx.x & 63) == (uint32_t)__ffsll(peers) - 1)
+                atomicAdd(&guniq[idx], (unsigned long long)__popcll(peers));
+            return;
+        }
+    }
+    atomicAdd(&guniq[idx], 1ull);
+}
+
+template <bool FILTER>
+__global__ void __launch_bounds__(256)
+k_query_uniq(SegView s, QuerySpec q, UniqSpec us, uint32_t n,
+             uint64_t base_row,
+             uint64_t* __restrict__ gkeys, uint64_t* __restrict__ graw,
+             uint32_t cap_mask,
+             unsigned long long* __restrict__ guniq,  // [cap][QMAX_UNIQ]
+             uint64_t* __restrict__ pkeys, uint32_t pcap_mask,
+             uint32_t* __restrict__ overflow) {  // [0] group, [1] pair table
+    // The filter may say "not seen" of a pair that was seen (an evicted or
+    // raced slot: one redundant global probe, which finds the pair claimed)
+    // but never "seen" of one that was not: a slot only ever holds a whole
+    // pair hash that some thread of this block stored on its way to
+    // table_claim, or 0, which no pair equals. Whole, because the slot is
+    // one naturally aligned 8-byte word read and written by relaxed atomic
+    // load/store (one ds_read_b64 / ds_write_b64 each): C++ atomics do
+    // not tear, so a read returns what ONE store wrote, never the halves
+    // of two. No ordering is needed: the storing thread goes on to claim
+    // the pair itself, whoever else skips it.
+    __shared__ uint64_t seen[FILTER ? UNIQ_FILTER_SLOTS : 1];
+    if (FILTER) {
+        for (uint32_t sl = threadIdx.x; sl < UNIQ_FILTER_SLOTS;
+             sl += blockDim.x)
+            seen[sl] = EMPTY_KEY;
+        __syncthreads();
+    }
+    for (uint64_t i = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x;
+         i < n; i += (uint64_t)gridDim.x * blockDim.x) {
+        uint64_t row = base_row + i;
+        if (!eval_terms(s, row, q)) continue;
+        uint64_t kraw[QMAX_KEYS];
+        uint64_t h = 0x243F6A8885A308D3ull;
+        for (uint32_t k = 0; k < q.n_keys; k++) {
+            kraw[k] = src_value(s, row, q.keys[k].family, q.keys[k].idx,
+                                q.keys[k].bucket, q.time_base_s);
+            h = mix64(h ^ kraw[k] ^ ((uint64_t)k << 56));
+        }
+        if (h == EMPTY_KEY) h = 1;
+        for (uint32_t u = 0; u < us.n_uniq; u++) {
+            const QUniq& it = us.items[u];
+            uint64_t vh = UNIQ_SEED ^ ((uint64_t)(u + 1) * UNIQ_ITEM_MUL);
+            for (uint32_t j = 0; j < it.n_args; j++)
+                vh = mix64(vh ^ src_value(s, row, it.cols[j].family,
+                                          it.cols[j].idx, 0, q.time_base_s)
+                           ^ ((uint64_t)j << 56));
+            uint64_t pair = mix64(h ^ vh);
+            if (pair == EMPTY_KEY) pair = 1;
+            if (FILTER) {
+                uint32_t fi = (uint32_t)(pair >> UNIQ_FILTER_SHIFT) &
+                              (UNIQ_FILTER_SLOTS - 1);
+                if (__hip_atomic_load(&seen[fi], __ATOMIC_RELAXED,
+                                      __HIP_MEMORY_SCOPE_WORKGROUP) == pair)
+                    continue;
+                __hip_atomic_store(&seen[fi], pair, __ATOMIC_RELAXED,
+                                   __HIP_MEMORY_SCOPE_WORKGROUP);
+            }
+            bool claimed;
+            uint32_t ps = table_claim(pkeys, pcap_mask, pair,
+                                      (uint32_t)(mix64(pair) & pcap_mask),
+                                      &claimed);
+            if (ps == ROW_NONE) {
+                atomicAdd(&overflow[1], 1u);
+                continue;
+            }
+            if (!claimed) continue;
+            uint32_t g = group_claim(h, kraw, q.n_keys, gkeys, graw,
+                                     cap_mask);
+            if (g == GROUP_FULL) atomicAdd(&overflow[0], 1u);
+            else uniq_count_add(guniq, g * QMAX_UNIQ + u);
+        }
+    }
+}
+
 // ---- radix-partitioned group-by (high cardinality) ----
 // When the key cardinality is far above QAGG_NSLOT, the direct kernel
 // spills most rows to per-row global atomics. The partitioned path
@@ -2023,6 +2160,75 @@ int df_query_agg(const void* u64c, const void* u32c, const void* u8c,
                        (unsigned long long*)gvals, cap - 1,
                        (uint32_t*)overflow);
     return (int)hipGetLastError();
+}
+
+// K15 distinct counts: one launch per segment into the group table of
+// df_query_agg plus a query-scoped pair table (`pcap` slots, power of
+// two). overflow[0]: claimed pairs whose group found no slot; overflow[1]:
+// pairs that found no slot in the pair table. Either one non-zero means
+// "rerun with fresh, larger tables". use_filter = 0 runs without the
+// block-local LDS filter (same results; benchmarks/query_uniq.py).
+int df_query_uniq(const void* u64c, const void* u32c, const void* u8c,
+                  const void* didc,
+                  const void* kg_tk, const void* kg_tv, uint32_t kg_cap,
+                  const void* attr_pool,
+                  const void* attr_start, const void* attr_cnt,
+                  const void* str_rowref, const void* str_lens,
+                  const void* pool,
+                  uint64_t stride, uint64_t n_rows,
+                  const void* spec, const void* uspec,
+                  uint32_t n, uint64_t base_row,
+                  void* gkeys, void* graw, uint32_t cap, void* guniq,
+                  void* pkeys, uint32_t pcap, void* overflow,
+                  uint32_t use_filter, uint64_t stream) {
+    SegView s{(const uint64_t*)u64c, (const uint32_t*)u32c, (const uint8_t*)u8c,
+              (const uint32_t*)didc,
+              (const uint64_t*)kg_tk, (const uint32_t*)kg_tv,
+              kg_cap ? kg_cap - 1 : 0,
+              (const int32_t*)attr_pool, (const uint32_t*)attr_start,
+              (const uint8_t*)attr_cnt, (const uint64_t*)str_rowref,
+              (const int16_t*)str_lens,
+              (const uint8_t*)pool, stride, n_rows};
+    QuerySpec q;
+    __builtin_memcpy(&q, spec, sizeof(QuerySpec));
+    UniqSpec us;
+    __builtin_memcpy(&us, uspec, sizeof(UniqSpec));
+    // the kernel indexes items and columns by these counts, and masks its
+    // probes with cap - 1: refuse what would read or write out of bounds
+    if (us.n_uniq > QMAX_UNIQ || q.n_keys > QMAX_KEYS ||
+        q.n_terms > QMAX_TERMS || cap == 0 || (cap & (cap - 1)) ||
+        cap > (1u << 28) ||  // counter indices (slot * QMAX_UNIQ + u) are u32
+        pcap == 0 || (pcap & (pcap - 1)) || base_row + n > stride)
+        return (int)hipErrorInvalidValue;
+    for (uint32_t u = 0; u < us.n_uniq; u++)
+        if (us.items[u].n_args > QMAX_UNIQ_ARGS)
+            return (int)hipErrorInvalidValue;
+    if (n == 0 || us.n_uniq == 0) return 0;
+    uint32_t blocks = grid_for(n);
+    if (blocks > UNIQ_MAX_BLOCKS) blocks = UNIQ_MAX_BLOCKS;
+    if (use_filter)
+        hipLaunchKernelGGL(k_query_uniq<true>, dim3(blocks), dim3(BLOCK), 0,
+                           STREAM(stream), s, q, us, n, base_row,
+                           (uint64_t*)gkeys, (uint64_t*)graw, cap - 1,
+                           (unsigned long long*)guniq, (uint64_t*)pkeys,
+                           pcap - 1, (uint32_t*)overflow);
+    else
+        hipLaunchKernelGGL(k_query_uniq<false>, dim3(blocks), dim3(BLOCK), 0,
+                           STREAM(stream), s, q, us, n, base_row,
+                           (uint64_t*)gkeys, (uint64_t*)graw, cap - 1,
+                           (unsigned long long*)guniq, (uint64_t*)pkeys,
+                           pcap - 1, (uint32_t*)overflow);
+    return (int)hipGetLastError();
+}
+
+uint32_t df_uniq_spec_size() { return sizeof(UniqSpec); }
+
+// the constants tests/uniq_cases.py rebuilds the pair hash and the filter
+// index from
+void df_uniq_consts(uint64_t* seed, uint64_t* item_mul,
+                    uint32_t* filter_slots, uint32_t* filter_shift) {
+    *seed = UNIQ_SEED; *item_mul = UNIQ_ITEM_MUL;
+    *filter_slots = UNIQ_FILTER_SLOTS; *filter_shift = UNIQ_FILTER_SHIFT;
 }
 
 int df_qpart_agg(const void* u64c, const void* u32c, const void* u8c,

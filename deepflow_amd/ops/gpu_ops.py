@@ -227,6 +227,34 @@ def query_agg(seg, spec_bytes: bytes, base_row: int, n: int,
         overflow.data_ptr(), _stream()), "df_query_agg")
 
 
+def query_uniq(seg, spec_bytes: bytes, uniq_bytes: bytes, base_row: int,
+               n: int, gkeys: torch.Tensor, graw: torch.Tensor,
+               guniq: torch.Tensor, pkeys: torch.Tensor, kg=None, *,
+               overflow: torch.Tensor, use_filter: bool = True) -> None:
+    """K15 distinct counts of rows [base_row, base_row + n) into
+    guniq[cap, QMAX_UNIQ] (u64, caller zeroes it), slot-aligned with the
+    gkeys/graw group table of query_agg. pkeys: the query-scoped table of
+    seen (group, value tuple) pair hashes, u64[power of two], zeroed once
+    and shared by every segment's launch. overflow: u32[2] device counters
+    (caller zeroes them): [0] pairs whose group found no slot, [1] pairs
+    that found no slot in pkeys; non-zero means 'rerun with fresh, larger
+    tables'."""
+    from ..query.spec import QMAX_KEYS, QMAX_UNIQ
+    lib = native.gpu()
+    assert base_row + n <= seg.capacity
+    cap = gkeys.numel()
+    assert graw.numel() == cap * QMAX_KEYS and overflow.numel() >= 2
+    assert guniq.numel() == cap * QMAX_UNIQ
+    buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
+    ubuf = ctypes.create_string_buffer(uniq_bytes, len(uniq_bytes))
+    native.check(lib.df_query_uniq(
+        *_seg_args(seg, kg), ctypes.addressof(buf), ctypes.addressof(ubuf),
+        n, base_row, gkeys.data_ptr(), graw.data_ptr(), gkeys.numel(),
+        guniq.data_ptr(), pkeys.data_ptr(), pkeys.numel(),
+        overflow.data_ptr(), 1 if use_filter else 0, _stream()),
+        "df_query_uniq")
+
+
 def qpart_agg(seg, spec_bytes: bytes, base_row: int, n: int,
               counts: torch.Tensor, cursors: torch.Tensor,
               row_scratch: torch.Tensor,

@@ -148,6 +148,16 @@ def _decl_gpu(lib: ct.CDLL) -> None:
                                     u64]
     lib.df_spec_sizes.restype = ct.c_int
     lib.df_spec_sizes.argtypes = [p, p, p, p]
+    # K15 distinct counts (k_query_uniq in dfgpu.hip)
+    lib.df_query_uniq.restype = ct.c_int
+    lib.df_query_uniq.argtypes = [p, p, p, p, p, p, u32, p, p, p, p, p, p,
+                                  u64, u64, p, p, u32, u64, p, p, u32, p,
+                                  p, u32, p, u32, u64]
+    lib.df_uniq_spec_size.restype = u32
+    lib.df_uniq_spec_size.argtypes = []
+    lib.df_uniq_consts.restype = None
+    lib.df_uniq_consts.argtypes = [ct.POINTER(u64), ct.POINTER(u64),
+                                   ct.POINTER(u32), ct.POINTER(u32)]
     lib.df_sort_u64.restype = ct.c_int
     lib.df_sort_u64.argtypes = [p, p, u32, p, ct.POINTER(ct.c_uint64), u64]
     lib.df_pack_bits.restype = ct.c_int

@@ -72,17 +72,28 @@ def _merge_qrow(a, b):
 
 
 def merge_agg_partials(parts: List[Dict]) -> Dict:
-    """Merge per-rank {key_rows, aggs, agg_ops[, qhist]} by agg op."""
+    """Merge per-rank {key_rows, aggs, agg_ops[, qhist][, uniq]} by agg
+    op. Uniq counts pass through for a group that one part holds alone;
+    distinct counts do not add and value ids are shard-local, so a group
+    that arrives from two parts with Uniq data is an error."""
     agg_ops = next((p["agg_ops"] for p in parts if p["aggs"]), [])
     merged: Dict[tuple, list] = {}
     keys_of: Dict[tuple, list] = {}
     qof: Dict[tuple, list] = {}
+    uof: Dict[tuple, list] = {}
     for p in parts:
         qh = p.get("qhist")
+        un = p.get("uniq")
         for i, (key, agg) in enumerate(zip(p["key_rows"], p["aggs"])):
             k = tuple(tuple(x) if isinstance(x, list) else x for x in key)
             if qh is not None:
                 qof[k] = _merge_qrow(qof.get(k), qh[i])
+            if un is not None:
+                if k in uof:
+                    raise ValueError(
+                        f"Uniq does not merge across shards: group "
+                        f"{list(key)!r} has rows on more than one shard")
+                uof[k] = un[i]
             acc = merged.get(k)
             if acc is None:
                 merged[k] = list(agg)
@@ -99,6 +110,8 @@ def merge_agg_partials(parts: List[Dict]) -> Dict:
            "aggs": list(merged.values())}
     if qof:
         out["qdata"] = [qof.get(k) for k in merged]
+    if uof:
+        out["uniq"] = [uof.get(k) for k in merged]
     return out
 
 
@@ -182,7 +195,8 @@ class DistQueryEngine:
         merged = merge_agg_partials([p for p in parts])
         return self.engine.finalize_groups(sql, merged["key_rows"],
                                            merged["aggs"],
-                                           qdata=merged.get("qdata"))
+                                           qdata=merged.get("qdata"),
+                                           uniq=merged.get("uniq"))
 
     # ---------------------------------------------------- topN pushdown
     # Exchange O(world x K) groups instead of every group: each rank sends
@@ -205,7 +219,8 @@ class DistQueryEngine:
             parts = exchange_json(partial, self.device)
             merged = merge_agg_partials(parts)
             return self.engine.finalize_groups(sql, merged["key_rows"],
-                                               merged["aggs"])
+                                               merged["aggs"],
+                                               uniq=merged.get("uniq"))
         margin = 4 * k + 64
 
         def tup(key):
@@ -219,17 +234,24 @@ class DistQueryEngine:
         phase1 = {"key_rows": [key_rows[i] for i in top_idx],
                   "aggs": [aggs[i] for i in top_idx],
                   "agg_ops": partial["agg_ops"]}
+        uniq = partial.get("uniq")
+        if uniq is not None:
+            phase1["uniq"] = [uniq[i] for i in top_idx]
         parts = exchange_json(phase1, self.device)
         candidates = set()
         for p in parts:
             for key in p["key_rows"]:
                 candidates.add(tup(key))
-        local = {tup(kr): (kr, a) for kr, a in zip(key_rows, aggs)}
+        local = {tup(kr): (kr, a, i)
+                 for i, (kr, a) in enumerate(zip(key_rows, aggs))}
         delta_keys = [c for c in candidates if c in local and c not in sent]
         phase2 = {"key_rows": [local[c][0] for c in delta_keys],
                   "aggs": [local[c][1] for c in delta_keys],
                   "agg_ops": partial["agg_ops"]}
+        if uniq is not None:
+            phase2["uniq"] = [uniq[local[c][2]] for c in delta_keys]
         parts2 = exchange_json(phase2, self.device)
         merged = merge_agg_partials(parts + parts2)
         return self.engine.finalize_groups(sql, merged["key_rows"],
-                                           merged["aggs"])
+                                           merged["aggs"],
+                                           uniq=merged.get("uniq"))

@@ -168,6 +168,16 @@ def _plan_needed(plan) -> Optional[Dict]:
     for m in plan.agg_meta:
         if "family" in m:
             add(m["family"], m["idx"])
+    for item in plan.uniqs:
+        for fam, idx in item.cols:
+            if fam == Q.SRC_TRACE128:
+                # binary id columns plus the pooled-string fallback
+                for c in (("trace_id_hi", "trace_id_lo") if idx == 0
+                          else ("span_id_b",)):
+                    add(Q.SRC_U64, S.U64_COLS.index(c))
+                add(Q.SRC_STR_HASH, 0)
+            else:
+                add(fam, idx)
     return need
 
 
@@ -454,6 +464,10 @@ class QueryEngine:
             # shipping (satisfied, tolerated, total) counts per group.
             out["qhist"] = self._quantile_partial(plan, segments, q_metas,
                                                   raw_keys)
+        if plan.uniqs:
+            # exact shard-local distinct counts: they pass through the
+            # merge for a group that lives on one shard only
+            out["uniq"] = [g["uniq"] for g in groups]
         return out
 
     _QH_SCALE = 16  # histogram sub-buckets per value octave
@@ -496,11 +510,12 @@ class QueryEngine:
         return out
 
     def finalize_groups(self, sql: str, key_rows, aggs,
-                        qdata=None) -> Dict:
+                        qdata=None, uniq=None) -> Dict:
         """Turn merged (hydrated keys, raw aggs) back into a result table
         using the local plan (column names, avg division, order/limit).
         `qdata` carries merged quantile histograms / apdex counts per
-        group (aligned with key_rows), from the distributed merge."""
+        group (aligned with key_rows), from the distributed merge; `uniq`
+        the per-group Uniq counts (aligned the same way)."""
         m = _FROM_RE.search(sql)
         table = m.group(1).lower() if m else "l7_flow_log"
         if table == "l4_flow_log":
@@ -529,6 +544,10 @@ class QueryEngine:
                     qi += 1
                     ai += 1
                     row.append(self._finish_qdata(meta, q))
+                elif meta["op"] == "uniq":
+                    row.append(uniq[gi][meta["uniq"]]
+                               if uniq and uniq[gi] else None)
+                    ai += 1
                 else:
                     row.append(agg[ai])
                     ai += 1
@@ -625,6 +644,9 @@ class QueryEngine:
                         c0 = int(counts[gi])
                         row.append(self._finish_quantile(
                             meta, svals[s0:s0 + c0]))
+                elif meta["op"] == "uniq":
+                    row.append(g["uniq"][meta["uniq"]])
+                    ai += 1
                 else:
                     row.append(g["agg"][ai])
                     ai += 1
@@ -841,9 +863,15 @@ class QueryEngine:
                 out = out[: plan.limit]
             return {"columns": cols, "values": out}
         groups: Dict[tuple, list] = {}
+        usets: Dict[tuple, list] = {}  # Uniq: host sets of value tuples
         for r in filtered:
             key = tuple(val(r, k.family, k.idx, k.bucket) for k in plan.keys)
             acc = groups.setdefault(key, [None] * len(plan.aggs))
+            if plan.uniqs:
+                sets = usets.setdefault(key, [set() for _ in plan.uniqs])
+                for ui, item in enumerate(plan.uniqs):
+                    sets[ui].add(tuple(val(r, fam, idx)
+                                       for fam, idx in item.cols))
             for ai, a in enumerate(plan.aggs):
                 v = 1 if a.op == Q.AGGOP_COUNT else val(r, a.family, a.idx)
                 cur = acc[ai]
@@ -863,6 +891,9 @@ class QueryEngine:
                     s_, c_ = acc[ai] or 0, acc[ai + 1] or 0
                     ai += 2
                     row.append(s_ / c_ if c_ else None)
+                elif meta["op"] == "uniq":
+                    row.append(len(usets[key][meta["uniq"]]))
+                    ai += 1
                 else:
                     row.append(acc[ai])
                     ai += 1

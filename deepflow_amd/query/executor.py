@@ -18,11 +18,16 @@ from .spec import (Plan, SRC_U64, SRC_U32, SRC_U8, SRC_DID, SRC_KG,
                    SRC_ATTR_MATCH, SRC_TRACE128, STR_FILTER_SEED,
                    OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_BETWEEN,
                    AGGOP_COUNT, AGGOP_SUM, AGGOP_MIN, AGGOP_MAX,
-                   QMAX_KEYS, QMAX_AGGS)
+                   QMAX_KEYS, QMAX_AGGS, QMAX_UNIQ)
 
 U64MAX = (1 << 64) - 1
 GROUP_CAP = 1 << 20       # first-try group table slots (power of two)
 GROUP_CAP_MAX = 1 << 24   # growth limit when the kernels report overflow
+# K15 Uniq pair table (one u64 per distinct (group, value tuple) pair):
+# first try min(pow2ceil(2 * rows * items), UNIQ_PAIR_CAP_FIRST_MAX), then
+# x4 per rerun while the kernel reports a full table, up to the limit
+UNIQ_PAIR_CAP_FIRST_MAX = 1 << 22
+UNIQ_PAIR_CAP_MAX = 1 << 28
 
 
 def _src_np(seg, family: int, idx: int, bucket: int, time_base_s: int,
@@ -159,6 +164,8 @@ def _mask_np(seg, plan: Plan, n: int, kg=None) -> np.ndarray:
 
 def execute_agg_cpu(plan: Plan, segments, kg=None) -> List[Dict]:
     groups: Dict[tuple, List[int]] = {}
+    # Uniq/UniqExact: per group, one set of value tuples per item
+    usets: Dict[tuple, List[set]] = {}
     for seg in segments:
         n = seg.n_rows
         if n == 0:
@@ -176,6 +183,9 @@ def execute_agg_cpu(plan: Plan, segments, kg=None) -> List[Dict]:
             else:
                 aggvals.append(_src_np(seg, a.family, a.idx, 0,
                                        plan.time_base_s, n, kg=kg)[mask])
+        ucols = [[_src_np(seg, fam, idx, 0, plan.time_base_s, n,
+                          kg=kg)[mask].tolist() for fam, idx in item.cols]
+                 for item in plan.uniqs]
         nk = len(keys)
         rows = int(mask.sum())
         key_tup = np.empty((rows, nk), dtype=np.uint64)
@@ -190,6 +200,9 @@ def execute_agg_cpu(plan: Plan, segments, kg=None) -> List[Dict]:
                     acc.append(0 if a.op in (AGGOP_COUNT, AGGOP_SUM)
                                else (U64MAX if a.op == AGGOP_MIN else 0))
                 groups[kt] = acc
+                usets[kt] = [set() for _ in plan.uniqs]
+            for ui, cols in enumerate(ucols):
+                usets[kt][ui].add(tuple(c[r] for c in cols))
             for ai, a in enumerate(plan.aggs):
                 v = int(aggvals[ai][r])
                 if a.op in (AGGOP_COUNT, AGGOP_SUM):
@@ -198,6 +211,10 @@ def execute_agg_cpu(plan: Plan, segments, kg=None) -> List[Dict]:
                     acc[ai] = min(acc[ai], v)
                 else:
                     acc[ai] = max(acc[ai], v)
+    if plan.uniqs:
+        return [{"key": list(k), "agg": list(v),
+                 "uniq": [len(x) for x in usets[k]]}
+                for k, v in groups.items()]
     return [{"key": list(k), "agg": list(v)} for k, v in groups.items()]
 
 
@@ -257,6 +274,41 @@ def _agg_pass_gpu(plan: Plan, segments, dev, kg, cap: int, use_qpart: bool):
     return gkeys, graw, gvals, lost
 
 
+def _uniq_pass_gpu(plan: Plan, segments, dev, kg, gkeys, graw):
+    """The K15 distinct-count pass: one k_query_uniq launch per segment
+    into the group table the aggregation pass filled, with one query-scoped
+    pair table shared by all segments (distinctness is across segments).
+    -> (guniq [cap, QMAX_UNIQ], pairs whose group found no slot)."""
+    from ..ops import gpu_ops
+    cap = gkeys.numel()
+    rows = sum(seg.n_rows for seg in segments)
+    want = 2 * max(rows, 1) * len(plan.uniqs)
+    pcap = min(1 << (want - 1).bit_length(), UNIQ_PAIR_CAP_FIRST_MAX)
+    spec, uspec = plan.to_bytes(), plan.uniq_to_bytes()
+    while True:
+        guniq = torch.zeros((cap, QMAX_UNIQ), dtype=torch.int64, device=dev)
+        # the two overflow counters ride behind the pair words
+        pbuf = torch.zeros(pcap + 1, dtype=torch.int64, device=dev)
+        pkeys, overflow = pbuf[:pcap], pbuf[pcap:].view(torch.int32)
+        for seg in segments:
+            if seg.n_rows == 0:
+                continue
+            gpu_ops.query_uniq(seg, spec, uspec, 0, seg.n_rows, gkeys, graw,
+                               guniq, pkeys, kg=kg, overflow=overflow)
+        # one read-back is the wait for the launches above
+        group_lost, pair_lost = (int(x) & 0xFFFFFFFF
+                                 for x in overflow.tolist())
+        if not pair_lost:
+            return guniq, group_lost
+        if pcap >= UNIQ_PAIR_CAP_MAX:
+            raise RuntimeError(
+                f"Uniq meets more than {UNIQ_PAIR_CAP_MAX} distinct "
+                f"(group, value) pairs (pair table limit); narrow the "
+                f"filter or the key set")
+        del guniq, pbuf, pkeys, overflow
+        pcap = min(pcap * 4, UNIQ_PAIR_CAP_MAX)
+
+
 def execute_agg_gpu(plan: Plan, segments, device="cuda", kg=None) -> List[Dict]:
     dev = torch.device(device)
     key_sig = tuple((k.family, k.idx, k.bucket) for k in plan.keys)
@@ -266,6 +318,12 @@ def execute_agg_gpu(plan: Plan, segments, device="cuda", kg=None) -> List[Dict]:
     while True:
         gkeys, graw, gvals, lost = _agg_pass_gpu(plan, segments, dev, kg,
                                                  cap, use_qpart)
+        guniq = None
+        if plan.uniqs and not lost:
+            # always the direct kernel: use_qpart only decides how the
+            # aggregation pass above runs
+            guniq, lost = _uniq_pass_gpu(plan, segments, dev, kg, gkeys,
+                                         graw)
         if not lost:
             break
         # the kernels leave rows of groups that found no slot out of the
@@ -274,7 +332,7 @@ def execute_agg_gpu(plan: Plan, segments, device="cuda", kg=None) -> List[Dict]:
             raise RuntimeError(
                 f"GROUP BY produces more than {GROUP_CAP_MAX} groups "
                 f"(group table limit); narrow the filter or the key set")
-        del gkeys, graw, gvals
+        del gkeys, graw, gvals, guniq
         cap = min(cap * 4, GROUP_CAP_MAX)
     mask = gkeys != 0
     raw = graw[mask].cpu().numpy().view(np.uint64)
@@ -285,6 +343,10 @@ def execute_agg_gpu(plan: Plan, segments, device="cuda", kg=None) -> List[Dict]:
     raw_l = raw[:, :nk].tolist()
     vals_l = vals[:, :na].tolist()
     out = [{"key": k, "agg": v} for k, v in zip(raw_l, vals_l)]
+    if guniq is not None:
+        nu = len(plan.uniqs)
+        for g, u in zip(out, guniq[mask].cpu()[:, :nu].tolist()):
+            g["uniq"] = u
     if plan.keys:
         _CARDINALITY_CACHE[key_sig] = len(out)
     return out

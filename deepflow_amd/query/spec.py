@@ -12,6 +12,9 @@ from typing import List, Optional
 QMAX_TERMS = 16
 QMAX_KEYS = 4
 QMAX_AGGS = 8
+# K15 distinct counts: a second POD next to QuerySpec (which must not grow)
+QMAX_UNIQ = 4
+QMAX_UNIQ_ARGS = 4
 
 # source families (dfgpu.hip enum)
 SRC_U64 = 0
@@ -30,6 +33,14 @@ SRC_TRACE128 = 10
 
 # seed for pooled-string filter hashing (twin: dfgpu.hip STR_FILTER_SEED)
 STR_FILTER_SEED = 0x5157A15E5EED
+
+# seed of the Uniq pair hash (twin: dfgpu.hip UNIQ_SEED; the formula is in
+# k_query_uniq's comment)
+UNIQ_SEED = 0x13198A2E03707344
+# families src_value reads for a Uniq argument (SRC_ATTR_VAL is per-slot,
+# not per-name, and SRC_ATTR_MATCH is a filter)
+UNIQ_FAMILIES = frozenset((SRC_U64, SRC_U32, SRC_U8, SRC_DID, SRC_KG,
+                           SRC_STR_HASH, SRC_TRACE128, SRC_TIME_BUCKET))
 
 OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_BETWEEN = range(7)
 AGGOP_COUNT, AGGOP_SUM, AGGOP_MIN, AGGOP_MAX = range(4)
@@ -63,6 +74,19 @@ class QuerySpecC(ct.Structure):
                 ("time_base_s", ct.c_uint64)]
 
 
+class QUniqColC(ct.Structure):
+    _fields_ = [("family", ct.c_uint8), ("idx", ct.c_uint16)]
+
+
+class QUniqC(ct.Structure):
+    _fields_ = [("cols", QUniqColC * QMAX_UNIQ_ARGS),
+                ("n_args", ct.c_uint32)]
+
+
+class UniqSpecC(ct.Structure):
+    _fields_ = [("items", QUniqC * QMAX_UNIQ), ("n_uniq", ct.c_uint32)]
+
+
 @dataclass
 class Term:
     family: int
@@ -88,6 +112,13 @@ class Agg:
 
 
 @dataclass
+class Uniq:
+    """One Uniq/UniqExact item: the (family, idx) columns of its value
+    tuple, in argument order."""
+    cols: List[tuple] = field(default_factory=list)
+
+
+@dataclass
 class Plan:
     table: str = "l7_flow_log"
     terms: List[Term] = field(default_factory=list)
@@ -106,6 +137,9 @@ class Plan:
     select_rows: bool = False  # non-aggregated SELECT
     select_cols: List[str] = field(default_factory=list)
     impossible: bool = False   # filter references unknown dict string
+    # distinct-count items; each also owns an AGGOP_COUNT placeholder in
+    # `aggs` (as percentile does) so agg_meta walks stay aligned
+    uniqs: List[Uniq] = field(default_factory=list)
 
     def to_bytes(self) -> bytes:
         c = QuerySpecC()
@@ -123,4 +157,15 @@ class Plan:
         c.n_terms, c.n_keys, c.n_aggs = (len(self.terms), len(self.keys),
                                          len(self.aggs))
         c.time_base_s = self.time_base_s
+        return bytes(memoryview(c))
+
+    def uniq_to_bytes(self) -> bytes:
+        c = UniqSpecC()
+        assert len(self.uniqs) <= QMAX_UNIQ
+        for u, item in enumerate(self.uniqs):
+            assert 1 <= len(item.cols) <= QMAX_UNIQ_ARGS
+            for j, (family, idx) in enumerate(item.cols):
+                c.items[u].cols[j] = QUniqColC(family=family, idx=idx)
+            c.items[u].n_args = len(item.cols)
+        c.n_uniq = len(self.uniqs)
         return bytes(memoryview(c))

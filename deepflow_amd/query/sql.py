@@ -6,6 +6,8 @@ server/querier/engine/clickhouse/clickhouse.go TransSelect/Where/GroupBy):
   SELECT item[, ...] FROM table [WHERE cond AND ...]
       [GROUP BY gitem[, ...]] [ORDER BY oitem [ASC|DESC][, ...]] [LIMIT n]
   item  := Func(metric) [AS alias] | tag [AS alias]
+         | Uniq(name[, name, name, name]) [AS alias]   (also UniqExact;
+           both are the exact distinct count of the value tuple)
   Func  := Count | Sum | Avg | Max | Min
   cond  := tag op literal | time >= n | time <= n
   gitem := tag | time(seconds)
@@ -29,7 +31,11 @@ _TOKEN_RE = re.compile(
 
 AGG_FUNCS = {"count": Q.AGGOP_COUNT, "sum": Q.AGGOP_SUM, "avg": None,
              "max": Q.AGGOP_MAX, "min": Q.AGGOP_MIN,
-             "percentile": None, "apdex": None}
+             "percentile": None, "apdex": None,
+             "uniq": None, "uniqexact": None}
+# exact distinct counts of a value tuple, Func(a[, b, c, d]); both
+# spellings mean the same here (the reference's Uniq is approximate)
+UNIQ_FUNCS = ("uniq", "uniqexact")
 
 
 class SqlError(ValueError):
@@ -92,6 +98,47 @@ def _resolve_tag(name: str, tags) -> TagDef:
     return t
 
 
+def _parse_uniq_args(p: Parser, func: str) -> List[str]:
+    """The identifier list of Uniq(a[, b, c, d]), after its '('."""
+    args: List[str] = []
+    if p.peek() == ("op", ")"):
+        p.next()
+        raise SqlError(f"{func}() needs 1 to {Q.QMAX_UNIQ_ARGS} arguments, "
+                       f"got none")
+    while True:
+        a = p.next()
+        if a == ("op", "*"):
+            raise SqlError(f"{func}(*) is not supported: name the columns")
+        if a[0] != "id":
+            raise SqlError(f"{func}: expected a tag or metric name, "
+                           f"got {a[1]!r}")
+        args.append(a[1])
+        nxt = p.next()
+        if nxt == ("op", ")"):
+            break
+        if nxt != ("op", ","):
+            raise SqlError(f"{func}: expected , or ) after {a[1]!r}")
+    if len(args) > Q.QMAX_UNIQ_ARGS:
+        raise SqlError(f"{func} takes at most {Q.QMAX_UNIQ_ARGS} arguments, "
+                       f"got {len(args)}")
+    return args
+
+
+def _uniq_col(name: str, func: str, tags, metrics) -> tuple:
+    """(family, idx) of one Uniq argument."""
+    if name.startswith("attribute."):
+        raise SqlError(f"{func} over attribute.* is not supported "
+                       f"({name!r})")
+    if name.lower() == "time":
+        return (Q.SRC_TIME_BUCKET, 0)
+    md = metrics.get(name) or _resolve_tag(name, tags)
+    if md.family not in Q.UNIQ_FAMILIES and \
+            getattr(md, "hydrate", None) != "raw":
+        raise SqlError(f"{func} cannot read {name!r} (source family "
+                       f"{md.family})")
+    return (md.family, md.idx)
+
+
 def parse_sql(sql: str, dictionary=None, time_base_s: int = 0,
               tags=None, metrics=None, name_maps=None) -> Q.Plan:
     """Parse DF-SQL into a Plan against a table's tag map (default:
@@ -114,6 +161,17 @@ def parse_sql(sql: str, dictionary=None, time_base_s: int = 0,
                 p.peek() == ("op", "("):
             func = t[1].lower()
             p.next()  # (
+            if func in UNIQ_FUNCS:
+                args = _parse_uniq_args(p, t[1])
+                alias = f"{func}({', '.join(args)})"
+                if p.kw_is("as"):
+                    p.next()
+                    alias = p.next()[1]
+                select_items.append(("agg", func, (args, None), alias))
+                if p.peek() == ("op", ","):
+                    p.next()
+                    continue
+                break
             arg_t = p.next()
             arg = arg_t[1] if arg_t[1] != "*" else "*"
             param = None
@@ -313,6 +371,18 @@ def parse_sql(sql: str, dictionary=None, time_base_s: int = 0,
                 plan.aggs.append(Q.Agg(Q.AGGOP_COUNT))
                 plan.agg_names.append(alias)
                 plan.agg_meta.append({"op": "avg"})
+            elif func in UNIQ_FUNCS:
+                # executed as a second kernel pass (k_query_uniq); the
+                # COUNT placeholder keeps the agg_meta walks aligned
+                if len(plan.uniqs) >= Q.QMAX_UNIQ:
+                    raise SqlError(f"at most {Q.QMAX_UNIQ} Uniq/UniqExact "
+                                   f"items in one query")
+                cols = [_uniq_col(a, func, tags, metrics) for a in arg_name]
+                plan.agg_meta.append({"op": "uniq", "uniq": len(plan.uniqs),
+                                      "cols": cols})
+                plan.uniqs.append(Q.Uniq(cols))
+                plan.aggs.append(Q.Agg(Q.AGGOP_COUNT))
+                plan.agg_names.append(alias)
             elif func in ("percentile", "apdex"):
                 # executed as a second pass over gathered values
                 md = metrics.get(arg_name) or _resolve_tag(arg_name, tags)

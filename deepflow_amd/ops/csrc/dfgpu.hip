@@ -1250,7 +1250,12 @@ enum {
     SRC_TRACE128,
 };
 // filter ops
-enum { OP_EQ = 0, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_BETWEEN };
+// OP_INSET / OP_NOT_INSET (K16): v0 is the device address of a u32 bitmap,
+// v1 its length in bits; the value is a member when it is below v1 and its
+// bit is set. A value outside the bitmap (DICT_ID_INVALID among them) is
+// not in the set, so it fails OP_INSET and passes OP_NOT_INSET.
+enum { OP_EQ = 0, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_BETWEEN,
+       OP_INSET, OP_NOT_INSET };
 // agg ops
 enum { AGGOP_COUNT = 0, AGGOP_SUM, AGGOP_MIN, AGGOP_MAX };
 
@@ -1347,6 +1352,14 @@ DEV bool eval_terms(const SegView& s, uint64_t row, const QuerySpec& q) {
             case OP_GT: ok = v > term.v0; break;
             case OP_GE: ok = v >= term.v0; break;
             case OP_BETWEEN: ok = v >= term.v0 && v <= term.v1; break;
+            case OP_INSET:
+            case OP_NOT_INSET: {
+                bool in = v < term.v1 &&
+                    ((reinterpret_cast<const uint32_t*>(term.v0)[v >> 5]
+                      >> (v & 31)) & 1);
+                ok = in == (term.op == OP_INSET);
+                break;
+            }
             default: ok = true;
         }
         if (term.group == 0) {
@@ -2337,6 +2350,12 @@ int df_spec_sizes(uint32_t* qterm, uint32_t* qkey, uint32_t* qagg, uint32_t* qsp
     *qterm = sizeof(QTerm); *qkey = sizeof(QKey); *qagg = sizeof(QAgg);
     *qspec = sizeof(QuerySpec);
     return 0;
+}
+
+// out[0..1]: OP_INSET, OP_NOT_INSET (query/spec.py carries the same two)
+void df_query_set_ops(uint32_t* out) {
+    out[0] = OP_INSET;
+    out[1] = OP_NOT_INSET;
 }
 
 int df_pack_bits(const void* src, uint32_t n, uint32_t base, uint32_t bits,

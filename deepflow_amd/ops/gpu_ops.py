@@ -287,6 +287,55 @@ def query_select(seg, spec_bytes: bytes, base_row: int, n: int,
 
 
 # ----------------------------------------------------------------------
+# K16: LIKE / REGEXP on dictionary tags (dfdict.hip). `arena` is a
+# store.dictionary.DictArena on the GPU.
+# ----------------------------------------------------------------------
+
+def query_set_ops():
+    """(OP_INSET, OP_NOT_INSET) as eval_terms was built with."""
+    out = (ctypes.c_uint32 * 2)()
+    native.gpu().df_query_set_ops(out)
+    return int(out[0]), int(out[1])
+
+
+def dict_re_limits():
+    """(table bytes, byte classes) k_dict_match was built for;
+    query/logregex.py carries the same two."""
+    out = (ctypes.c_uint32 * 2)()
+    native.gpu().df_dict_re_limits(out)
+    return int(out[0]), int(out[1])
+
+
+def dict_regex_table(rx, device) -> torch.Tensor:
+    """rx's tables on `device`, padded to the 16-byte chunks the kernel
+    stages them in."""
+    table = rx.table()
+    blob = np.zeros((table.nbytes + 15) & ~15, dtype=np.uint8)
+    blob[:table.nbytes] = table
+    return torch.from_numpy(blob).to(device)
+
+
+def dict_match(arena, rx, words: torch.Tensor, n_bits: int, *,
+               first: int = 0, n_entries: int = None,
+               complement: bool = False,
+               table: torch.Tensor = None) -> None:
+    """Set bit id of `words` (u32 bitmap of n_bits bits, caller zeroes it)
+    for every arena entry in [first, n_entries) that rx (a
+    query.logregex.LogRegex) matches, or with `complement` for every entry
+    it does not match. Ids outside the bitmap are skipped."""
+    n_entries = arena.n if n_entries is None else n_entries
+    assert 0 <= first and n_entries <= arena.n
+    assert words.dtype == torch.int32 and n_bits <= words.numel() * 32
+    if table is None:
+        table = dict_regex_table(rx, words.device)
+    native.check(native.gpu().df_dict_match(
+        arena.data.data_ptr(), arena.off.data_ptr(), arena.lens.data_ptr(),
+        arena.ids.data_ptr(), first, n_entries, table.data_ptr(),
+        rx.n_states, rx.n_classes, rx.flags, 1 if complement else 0,
+        words.data_ptr(), n_bits, _stream()), "df_dict_match")
+
+
+# ----------------------------------------------------------------------
 # K9: profile store ingest + flame fold (dfprofile.hip). `st` is a
 # store.profile_store.GpuProfileStore (owns every tensor named here).
 # ----------------------------------------------------------------------

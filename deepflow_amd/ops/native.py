@@ -158,6 +158,14 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_uniq_consts.restype = None
     lib.df_uniq_consts.argtypes = [ct.POINTER(u64), ct.POINTER(u64),
                                    ct.POINTER(u32), ct.POINTER(u32)]
+    # K16 set-membership filter ops and the dictionary walk (dfdict.hip)
+    lib.df_query_set_ops.restype = None
+    lib.df_query_set_ops.argtypes = [ct.POINTER(u32)]
+    lib.df_dict_re_limits.restype = None
+    lib.df_dict_re_limits.argtypes = [ct.POINTER(u32)]
+    lib.df_dict_match.restype = ct.c_int
+    lib.df_dict_match.argtypes = [p, p, p, p, u32, u32, p, u32, u32, u32,
+                                  u32, p, u32, u64]
     lib.df_sort_u64.restype = ct.c_int
     lib.df_sort_u64.argtypes = [p, p, u32, p, ct.POINTER(ct.c_uint64), u64]
     lib.df_pack_bits.restype = ct.c_int

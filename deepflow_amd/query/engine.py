@@ -835,6 +835,13 @@ class QueryEngine:
             if t.family == Q.SRC_CONST0:
                 return OPS[t.op](0, t.v0)
             v = val(r, t.family, t.idx)
+            if t.op in Q.SET_OPS:
+                # LIKE / REGEXP on a raw column: Python `re` on the row's
+                # value, None as the empty string
+                s = "" if v is None else str(v)
+                hit = plan.sets[t.v0].host_matches(
+                    s.encode("utf-8", "replace"))
+                return hit == (t.op == Q.OP_INSET)
             if t.op == Q.OP_BETWEEN:
                 return t.v0 <= v <= t.v1
             try:

@@ -17,6 +17,7 @@ from .spec import (Plan, SRC_U64, SRC_U32, SRC_U8, SRC_DID, SRC_KG,
                    SRC_ATTR_VAL, SRC_TIME_BUCKET, SRC_CONST0, SRC_STR_HASH,
                    SRC_ATTR_MATCH, SRC_TRACE128, STR_FILTER_SEED,
                    OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_BETWEEN,
+                   OP_INSET, OP_NOT_INSET, SET_OPS,
                    AGGOP_COUNT, AGGOP_SUM, AGGOP_MIN, AGGOP_MAX,
                    QMAX_KEYS, QMAX_AGGS, QMAX_UNIQ)
 
@@ -28,6 +29,78 @@ GROUP_CAP_MAX = 1 << 24   # growth limit when the kernels report overflow
 # x4 per rerun while the kernel reports a full table, up to the limit
 UNIQ_PAIR_CAP_FIRST_MAX = 1 << 22
 UNIQ_PAIR_CAP_MAX = 1 << 28
+
+
+# K16 counters, per process: id-set bitmaps built, k_dict_match launches
+SET_STATS = {"bitmaps": 0, "dict_match": 0}
+
+
+def _host_bitmap(ps):
+    """One PatternSet as (u32 words, bits) by Python `re` over the host
+    strings. This is the CPU engine's set and the oracle of k_dict_match,
+    so it never goes through the DFA. Name-map sets are built here for the
+    GPU too (the maps are small); there id 0 means 'no KG hit' and stays
+    out, like every id the map does not name: they behave as ''."""
+    if ps.name_map is not None:
+        items = ((int(i), str(nm).encode()) for i, nm in ps.name_map.items()
+                 if int(i) > 0)
+        nbits = max((int(i) for i in ps.name_map), default=0) + 1
+    else:
+        dom = ps.domain
+        items = ((i, s) for (d, i), s in ps.dictionary.id_to_str.items()
+                 if d == dom)
+        nbits = ps.dictionary.capacity
+    words = np.zeros((nbits + 31) // 32, dtype=np.uint32)
+    for i, s in items:
+        if i < nbits and ps.host_matches(s) != ps.complement:
+            words[i >> 5] |= np.uint32(1 << (i & 31))
+    return words, nbits
+
+
+def bind_sets(plan: Plan, device="cpu"):
+    """Build the bitmaps of the plan's OP_INSET / OP_NOT_INSET terms on
+    `device`, once per plan and device. -> (bitmaps, [(address, bits)]) or
+    None for a plan without such terms: numpy words and no addresses on the
+    CPU, device tensors and their addresses on the GPU. The plan keeps them
+    (Plan.bound), so they outlive every launch of its query."""
+    if not plan.has_sets():
+        return None
+    dev = torch.device(device)
+    if dev.type != "cpu" and dev.index is None:
+        dev = torch.device(dev.type, torch.cuda.current_device())
+    got = plan.bound.get(str(dev))
+    if got is not None:
+        return got
+    if dev.type == "cpu":
+        got = ([_host_bitmap(ps) for ps in plan.sets], None)
+    else:
+        from ..ops import gpu_ops
+        bitmaps, pairs = [], []
+        for ps in plan.sets:
+            if ps.name_map is not None:
+                words, nbits = _host_bitmap(ps)
+                t = torch.from_numpy(words.view(np.int32)).to(dev)
+            else:
+                nbits = ps.dictionary.capacity
+                t = torch.zeros((nbits + 31) // 32, dtype=torch.int32,
+                                device=dev)
+                arena = ps.dictionary.arena(ps.domain, dev)
+                if arena.n:
+                    gpu_ops.dict_match(arena, ps.rx, t, nbits,
+                                       complement=ps.complement)
+                    SET_STATS["dict_match"] += 1
+            SET_STATS["bitmaps"] += 1
+            bitmaps.append(t)
+            pairs.append((t.data_ptr(), nbits))
+        got = (bitmaps, pairs)
+    plan.bound[str(dev)] = got
+    return got
+
+
+def _spec_bytes(plan: Plan, dev) -> bytes:
+    """The kernel spec of `plan` with its id sets bound on `dev`."""
+    got = bind_sets(plan, dev)
+    return plan.to_bytes(sets=got[1] if got else None)
 
 
 def _src_np(seg, family: int, idx: int, bucket: int, time_base_s: int,
@@ -128,6 +201,13 @@ def _term_mask(seg, t, plan: Plan, n: int, kg=None) -> np.ndarray:
             out = ~out
         return out
     v = _src_np(seg, t.family, t.idx, 0, plan.time_base_s, n, kg=kg)
+    if t.op in SET_OPS:
+        words, nbits = bind_sets(plan, "cpu")[0][t.v0]
+        inside = v < np.uint64(nbits)
+        vi = np.where(inside, v, 0).astype(np.int64)
+        member = inside & (((words[vi >> 5] >> (vi & 31).astype(np.uint32))
+                            & np.uint32(1)) != 0)
+        return member if t.op == OP_INSET else ~member
     v0 = np.uint64(t.v0 & U64MAX)
     v1 = np.uint64(t.v1 & U64MAX)
     if t.op == OP_EQ:
@@ -254,7 +334,7 @@ def _agg_pass_gpu(plan: Plan, segments, dev, kg, cap: int, use_qpart: bool):
     for ai, a in enumerate(plan.aggs):
         if a.op == AGGOP_MIN:
             gvals[:, ai] = -1  # 0xFFFF.. as int64
-    spec = plan.to_bytes()
+    spec = _spec_bytes(plan, dev)
     for seg in segments:
         if seg.n_rows == 0:
             continue
@@ -284,7 +364,7 @@ def _uniq_pass_gpu(plan: Plan, segments, dev, kg, gkeys, graw):
     rows = sum(seg.n_rows for seg in segments)
     want = 2 * max(rows, 1) * len(plan.uniqs)
     pcap = min(1 << (want - 1).bit_length(), UNIQ_PAIR_CAP_FIRST_MAX)
-    spec, uspec = plan.to_bytes(), plan.uniq_to_bytes()
+    spec, uspec = _spec_bytes(plan, dev), plan.uniq_to_bytes()
     while True:
         guniq = torch.zeros((cap, QMAX_UNIQ), dtype=torch.int64, device=dev)
         # the two overflow counters ride behind the pair words
@@ -374,7 +454,7 @@ def execute_select_gpu(plan: Plan, segments, limit: int,
     from ..ops import gpu_ops
     dev = torch.device(device)
     out = []
-    spec = plan.to_bytes()
+    spec = _spec_bytes(plan, dev)
     for si, seg in enumerate(segments):
         if seg.n_rows == 0:
             continue
@@ -494,7 +574,7 @@ def _matching_rows_t(plan: Plan, seg, device, kg=None):
     cap = n
     out_rows = torch.zeros(cap, dtype=torch.int64, device=dev)
     out_ctr = torch.zeros(1, dtype=torch.int32, device=dev)
-    spec = plan.to_bytes()
+    spec = _spec_bytes(plan, dev)
     gpu_ops.query_select(seg, spec, 0, n, out_rows, out_ctr, kg=kg)
     torch.cuda.synchronize()
     cnt = min(int(out_ctr.item()), cap)
@@ -507,7 +587,9 @@ def execute_grouped_values(plan: Plan, segments, metas, device: str,
     {mi: (sorted_vals float64 cpu, starts, counts)}) for quantile
     finishing. Raises ValueError for unsupported key/metric families."""
     import copy
-    sub = copy.deepcopy(plan)
+    # shallow: only the flag changes, and the id sets bound by the
+    # aggregation pass (plan.bound) are shared, not rebuilt
+    sub = copy.copy(plan)
     sub.select_rows = True
     key_cols = [[] for _ in plan.keys]
     val_cols = [[] for _ in metas]

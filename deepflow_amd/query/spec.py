@@ -43,6 +43,14 @@ UNIQ_FAMILIES = frozenset((SRC_U64, SRC_U32, SRC_U8, SRC_DID, SRC_KG,
                            SRC_STR_HASH, SRC_TRACE128, SRC_TIME_BUCKET))
 
 OP_EQ, OP_NE, OP_LT, OP_LE, OP_GT, OP_GE, OP_BETWEEN = range(7)
+# K16 set membership (LIKE / REGEXP on dictionary tags): in the kernel spec
+# v0 is the device address of a u32 bitmap and v1 its length in bits; in a
+# Plan, until it is bound, v0 indexes Plan.sets. A value outside the bitmap
+# (DICT_ID_INVALID among them) is not a member.
+OP_INSET, OP_NOT_INSET = 7, 8
+SET_OPS = (OP_INSET, OP_NOT_INSET)
+# the largest id a host-built (kgname) set may hold: bitmaps stay <= 8 MiB
+SET_MAX_BITS = 1 << 26
 AGGOP_COUNT, AGGOP_SUM, AGGOP_MIN, AGGOP_MAX = range(4)
 
 OP_BY_NAME = {"=": OP_EQ, "==": OP_EQ, "!=": OP_NE, "<>": OP_NE, "<": OP_LT,
@@ -118,6 +126,32 @@ class Uniq:
     cols: List[tuple] = field(default_factory=list)
 
 
+@dataclass(eq=False)
+class PatternSet:
+    """Host description of one id set behind an OP_INSET / OP_NOT_INSET
+    term: the ids of a dictionary domain (or of a name map) whose string
+    matches a pattern, or, with `complement`, whose string does not. The
+    executor turns it into a bitmap on the plan's device before the first
+    launch (executor.bind_sets)."""
+    kind: str                       # 'like' | 'regexp'
+    pattern: str                    # as written in the query
+    regex: str                      # what is evaluated (LIKE: translated)
+    rx: object                      # logregex.LogRegex: DFA + host `re`
+    complement: bool = False
+    domain: Optional[int] = None    # dict:<domain> tags
+    dictionary: object = None       # the shard's TagDictionary
+    name_map: Optional[dict] = None  # kgname tags: id -> display name
+
+    def host_matches(self, value: bytes) -> bool:
+        """Python `re` on one string: the oracle of the DFA walk."""
+        if self.kind == "like":
+            return self.rx.host.fullmatch(value) is not None
+        return self.rx.host.search(value) is not None
+
+    def __deepcopy__(self, memo):
+        return self                 # never copy a dictionary with a plan
+
+
 @dataclass
 class Plan:
     table: str = "l7_flow_log"
@@ -140,16 +174,35 @@ class Plan:
     # distinct-count items; each also owns an AGGOP_COUNT placeholder in
     # `aggs` (as percentile does) so agg_meta walks stay aligned
     uniqs: List[Uniq] = field(default_factory=list)
+    # K16: the id sets of OP_INSET / OP_NOT_INSET terms (Term.v0 indexes
+    # this list), and what the executor bound them to, per device:
+    # {device: (bitmaps, [(address, bits), ...])}. The bitmaps live as long
+    # as the plan does, which is longer than any launch of its query.
+    sets: List[PatternSet] = field(default_factory=list)
+    bound: dict = field(default_factory=dict)
 
-    def to_bytes(self) -> bytes:
+    def has_sets(self) -> bool:
+        return any(t.op in SET_OPS for t in self.terms)
+
+    def to_bytes(self, sets=None) -> bytes:
+        """The kernel spec. `sets`: [(device address, bits)] per entry of
+        self.sets; a plan with set terms does not serialise without it (an
+        index must never travel as if it were a pointer)."""
         c = QuerySpecC()
         assert len(self.terms) <= QMAX_TERMS
         assert len(self.keys) <= QMAX_KEYS
         assert len(self.aggs) <= QMAX_AGGS
         for i, t in enumerate(self.terms):
+            v0, v1 = t.v0, t.v1
+            if t.op in SET_OPS:
+                if sets is None:
+                    raise RuntimeError(
+                        "plan has LIKE/REGEXP set terms that are not bound "
+                        "to device bitmaps (executor.bind_sets)")
+                v0, v1 = sets[t.v0]
             c.terms[i] = QTermC(family=t.family, op=t.op, idx=t.idx,
                                 group=getattr(t, "group", 0),
-                                v0=t.v0 & (2**64 - 1), v1=t.v1 & (2**64 - 1))
+                                v0=v0 & (2**64 - 1), v1=v1 & (2**64 - 1))
         for i, k in enumerate(self.keys):
             c.keys[i] = QKeyC(family=k.family, idx=k.idx, bucket=k.bucket)
         for i, a in enumerate(self.aggs):

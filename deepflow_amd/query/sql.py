@@ -10,11 +10,24 @@ server/querier/engine/clickhouse/clickhouse.go TransSelect/Where/GroupBy):
            both are the exact distinct count of the value tuple)
   Func  := Count | Sum | Avg | Max | Min
   cond  := tag op literal | time >= n | time <= n
+         | tag IN (literal, ...) | ( cond OR cond ... )
+         | tag [NOT] LIKE 'pattern' | tag [NOT] REGEXP 'pattern'
   gitem := tag | time(seconds)
   SHOW tags|metrics FROM table  (handled by the engine)
 
 String literals filter dict-encoded tags by compiling to SmartEncoding IDs
 at plan time (the analog of the reference's dictGet/ID rewrite).
+
+LIKE / REGEXP (K16; reference: engine/clickhouse/filter.go, `*` -> `%` for
+LIKE, REGEXP -> match()) take dictionary tags (dict:<domain>), name-map tags
+(kgname:*) and the raw columns of row tables and CTEs; every other tag is a
+SqlError. LIKE: `%` and `*` match any run of bytes, `_` one byte, `\\` makes
+the next character literal; the whole value must match, case-sensitively. A
+LIKE without a wildcard is an equality. REGEXP is an unanchored,
+case-sensitive re.search over the subset query/logregex.py documents. The
+pattern is matched once per distinct string (k_dict_match over the
+dictionary's device arena) and rows are filtered by the resulting id bitmap
+(OP_INSET / OP_NOT_INSET); an empty value behaves as the empty string.
 """
 from __future__ import annotations
 
@@ -224,10 +237,18 @@ def parse_sql(sql: str, dictionary=None, time_base_s: int = 0,
                 group_counter += 1
                 while True:
                     name = p.next()
-                    op_t = p.next()
-                    lit = p.next()
-                    _add_term(plan, name[1], op_t[1], lit, dictionary, tags,
-                              group=group_counter, name_maps=name_maps)
+                    pat_op = _pattern_op(p)
+                    if pat_op is not None:
+                        _add_pattern_term(plan, name[1], pat_op, p.next(),
+                                          dictionary, tags,
+                                          group=group_counter,
+                                          name_maps=name_maps)
+                    else:
+                        op_t = p.next()
+                        lit = p.next()
+                        _add_term(plan, name[1], op_t[1], lit, dictionary,
+                                  tags, group=group_counter,
+                                  name_maps=name_maps)
                     if p.kw_is("or"):
                         p.next()
                         continue
@@ -255,6 +276,9 @@ def parse_sql(sql: str, dictionary=None, time_base_s: int = 0,
                         if p.next() == ("op", ")"):
                             break
                         raise SqlError("expected , or ) in IN list")
+                elif (pat_op := _pattern_op(p)) is not None:
+                    _add_pattern_term(plan, name[1], pat_op, p.next(),
+                                      dictionary, tags, name_maps=name_maps)
                 else:
                     op_t = p.next()
                     if op_t[0] != "op" or op_t[1] not in Q.OP_BY_NAME:
@@ -407,6 +431,130 @@ def parse_sql(sql: str, dictionary=None, time_base_s: int = 0,
             cols.append(arg)
         plan.select_cols = cols
     return plan
+
+
+def _pattern_op(p: Parser):
+    """Consume `[NOT] LIKE` / `[NOT] REGEXP` if that is what comes next.
+    -> (kind, negated) or None (nothing consumed)."""
+    t = p.peek()
+    if t is None or t[0] != "id":
+        return None
+    word = t[1].lower()
+    if word in ("like", "regexp"):
+        p.next()
+        return word, False
+    if word == "not" and p.pos + 1 < len(p.toks):
+        nxt = p.toks[p.pos + 1]
+        if nxt[0] == "id" and nxt[1].lower() in ("like", "regexp"):
+            p.next()
+            p.next()
+            return nxt[1].lower(), True
+    return None
+
+
+def _re_literal(c: str) -> str:
+    if c.isalnum() or c == "_" or ord(c) > 127:
+        return c
+    return "\\" + c
+
+
+def like_to_regex(pattern: str):
+    """A LIKE pattern -> (regex, literal). `%` and `*` match any run of
+    bytes, `_` one byte, `\\` makes the next character literal, the rest is
+    literal; the regex is anchored at both ends and its wildcards are
+    [\\s\\S], so newlines are ordinary bytes. `literal` is the string the
+    pattern equals when it has no wildcard, else None."""
+    out, lit, wild = [r"\A"], [], False
+    i = 0
+    while i < len(pattern):
+        c = pattern[i]
+        if c == "\\" and i + 1 < len(pattern):
+            i += 1
+            c = pattern[i]
+            out.append(_re_literal(c))
+            lit.append(c)
+        elif c in "%*":
+            out.append(r"[\s\S]*")
+            wild = True
+        elif c == "_":
+            out.append(r"[\s\S]")
+            wild = True
+        else:
+            out.append(_re_literal(c))
+            lit.append(c)
+        i += 1
+    out.append(r"\Z")
+    return "".join(out), (None if wild else "".join(lit))
+
+
+def _add_pattern_term(plan: Q.Plan, name: str, pat_op, lit, dictionary,
+                      tags, group: int = 0, name_maps=None) -> None:
+    """tag [NOT] LIKE 'pat' / tag [NOT] REGEXP 'pat' (K16). On dictionary
+    and name-map tags the pattern becomes an id set (Plan.sets) and the term
+    a bit test; an empty value (DICT_ID_INVALID, KG id 0) must behave as the
+    empty string, so a pattern that matches b"" is stored as the set of ids
+    that do NOT match and the op is swapped."""
+    kind, negated = pat_op
+    word = ("NOT " if negated else "") + kind.upper()
+    if lit[0] != "str":
+        raise SqlError(f"{word} compares {name!r} against a string "
+                       f"literal, got {lit[1]!r}")
+    if name.startswith("attribute."):
+        raise SqlError(f"{word} is not supported on {name!r}: custom "
+                       f"attributes are filtered by = / != only")
+    if name.lower() == "time":
+        raise SqlError(f"{word} is not supported on 'time': it is numeric")
+    td = _resolve_tag(name, tags)
+    how = td.hydrate
+    is_dict = how.startswith("dict:")
+    is_kg = how.startswith("kgname:")
+    if not (is_dict or is_kg or how == "raw"):
+        why = {"strhash": "it is a pooled string, stored per row and not "
+                          "in the dictionary",
+               "tracebin": "trace and span ids are stored as binary hashes",
+               "ip6str": "IPv6 addresses are stored packed",
+               }.get(how, "it is not a dictionary-encoded string tag")
+        raise SqlError(f"{word} is not supported on {name!r}: {why}")
+    if kind == "like":
+        regex, literal = like_to_regex(lit[1])
+        if literal is not None:
+            # no wildcard: an equality, through the id lookup
+            _add_term(plan, name, "!=" if negated else "=",
+                      ("str", literal), dictionary, tags, group=group,
+                      name_maps=name_maps)
+            return
+    else:
+        regex = lit[1]
+    from .logregex import compile_log_regex
+    try:
+        rx = compile_log_regex(regex)
+    except ValueError as e:
+        raise SqlError(f"{word} {lit[1]!r} on {name!r}: {e}")
+    ps = Q.PatternSet(kind=kind, pattern=lit[1], regex=regex, rx=rx)
+    if how == "raw":
+        # row-table / CTE column: matched per row on the host
+        op = Q.OP_NOT_INSET if negated else Q.OP_INSET
+    else:
+        if is_dict:
+            if dictionary is None:
+                raise SqlError(
+                    f"{word} on {name!r} needs the shard's tag dictionary: "
+                    f"ids are shard-local and this plan was compiled "
+                    f"without one")
+            ps.domain = int(how.split(":")[1])
+            ps.dictionary = dictionary
+        else:
+            ps.name_map = (name_maps or {}).get(how.split(":", 1)[1], {})
+            top = max(ps.name_map, default=0)
+            if top >= Q.SET_MAX_BITS:
+                raise SqlError(
+                    f"{word} on {name!r}: the name map holds id {top}, "
+                    f"the limit is {Q.SET_MAX_BITS - 1}")
+        ps.complement = ps.host_matches(b"")
+        op = Q.OP_INSET if negated == ps.complement else Q.OP_NOT_INSET
+    plan.terms.append(Q.Term(td.family, td.idx, op, len(plan.sets),
+                             group=group))
+    plan.sets.append(ps)
 
 
 def _never(plan: Q.Plan, group: int) -> None:

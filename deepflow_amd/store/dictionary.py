@@ -50,6 +50,87 @@ def domain_seed(domain: int) -> int:
     return (0x9E3779B97F4A7C15 * (domain + 1)) & ((1 << 64) - 1)
 
 
+class DictArena:
+    """One dictionary domain's strings on a device, for k_dict_match (K16:
+    LIKE / REGEXP on dictionary tags): the entries' bytes back to back and
+    three columns per entry, byte offset (u32), id (u32) and length (u16).
+
+    Built lazily and only at query time: TagDictionary.arena() hands new
+    entries over as (id, bytes) in `pending`, upload() appends them with one
+    host-to-device copy of the bytes and one of the columns. Buffers grow by
+    doubling; old contents are copied on the device."""
+
+    MAX_BYTES = (1 << 32) - 1           # offsets are u32
+
+    def __init__(self, device):
+        self.device = torch.device(device)
+        self.n = 0                      # entries uploaded
+        self.nbytes = 0                 # arena bytes in use
+        self.data = torch.zeros(0, dtype=torch.uint8, device=self.device)
+        self.off = torch.zeros(0, dtype=torch.int32, device=self.device)
+        self.ids = torch.zeros(0, dtype=torch.int32, device=self.device)
+        self.lens = torch.zeros(0, dtype=torch.int16, device=self.device)
+        self.pending: List[Tuple[int, bytes]] = []
+        # counters (tests and benchmarks read them)
+        self.h2d_copies = 0
+        self.h2d_bytes = 0
+        self.uploads = 0
+
+    @staticmethod
+    def _grown(t: torch.Tensor, used: int, need: int, floor: int):
+        if need <= t.numel():
+            return t
+        cap = max(t.numel(), floor)
+        while cap < need:
+            cap *= 2
+        new = torch.zeros(cap, dtype=t.dtype, device=t.device)
+        new[:used].copy_(t[:used])      # device to device
+        return new
+
+    def upload(self) -> int:
+        """Append the pending entries. -> how many."""
+        new = self.pending
+        if not new:
+            return 0
+        self.pending = []
+        k = len(new)
+        lens = np.fromiter((len(s) for _, s in new), dtype=np.int64, count=k)
+        if int(lens.max()) > 0xFFFF:
+            raise RuntimeError("dictionary entry longer than 65535 bytes")
+        total = int(lens.sum())
+        if self.nbytes + total > self.MAX_BYTES:
+            raise RuntimeError("dictionary arena exceeds 4 GiB")
+        offs = self.nbytes + np.cumsum(lens) - lens
+        cols = np.empty(10 * k, dtype=np.uint8)
+        cols[:4 * k].view(np.uint32)[:] = offs
+        cols[4 * k:8 * k].view(np.uint32)[:] = np.fromiter(
+            (i for i, _ in new), dtype=np.int64, count=k)
+        cols[8 * k:].view(np.uint16)[:] = lens
+        self.data = self._grown(self.data, self.nbytes, self.nbytes + total,
+                                1 << 12)
+        self.off = self._grown(self.off, self.n, self.n + k, 1 << 8)
+        self.ids = self._grown(self.ids, self.n, self.n + k, 1 << 8)
+        self.lens = self._grown(self.lens, self.n, self.n + k, 1 << 8)
+        if total:
+            joined = np.frombuffer(b"".join(s for _, s in new),
+                                   dtype=np.uint8)
+            self.data[self.nbytes:self.nbytes + total].copy_(
+                torch.from_numpy(joined.copy()))
+            self.h2d_copies += 1
+            self.h2d_bytes += total
+        dcols = torch.from_numpy(cols).to(self.device)
+        self.h2d_copies += 1
+        self.h2d_bytes += cols.nbytes
+        n = self.n
+        self.off[n:n + k].copy_(dcols[:4 * k].view(torch.int32))
+        self.ids[n:n + k].copy_(dcols[4 * k:8 * k].view(torch.int32))
+        self.lens[n:n + k].copy_(dcols[8 * k:].view(torch.int16))
+        self.n += k
+        self.nbytes += total
+        self.uploads += 1
+        return k
+
+
 class TagDictionary:
     """Per-shard tag dictionary: GPU table + host id<->string maps."""
 
@@ -68,9 +149,43 @@ class TagDictionary:
         self.dropped = 0
         # entries discovered since the last cross-shard sync
         self.pending_sync: List[Tuple[int, int, bytes]] = []
+        # K16 device arenas, {domain: {device: DictArena}}, and how many
+        # entries of id_to_str (in insertion order) they have been offered
+        self._arenas: Dict[int, Dict[str, DictArena]] = {}
+        self._arena_seen = 0
 
     def n_entries(self) -> int:
         return len(self.id_to_str)
+
+    def arena(self, domain: int, device) -> DictArena:
+        """The domain's strings on `device`, caught up with id_to_str.
+
+        Nothing on the ingest path knows about arenas: whatever put entries
+        into id_to_str (harvest, import_entries, a restored checkpoint), a
+        dict keeps insertion order and entries are never removed, so the
+        entries past `_arena_seen` are exactly the new ones. They are read
+        from the dict's end, so a catch-up costs O(new entries), and O(1)
+        when there are none."""
+        n = len(self.id_to_str)
+        new = n - self._arena_seen
+        if new:
+            if self._arenas:
+                import itertools
+                tail = list(itertools.islice(
+                    reversed(self.id_to_str.items()), new))
+                for (dom, slot), s in reversed(tail):
+                    for a in self._arenas.get(dom, {}).values():
+                        a.pending.append((slot, s))
+            self._arena_seen = n
+        per_dev = self._arenas.setdefault(domain, {})
+        a = per_dev.get(str(device))
+        if a is None:
+            # first use: the one walk over the whole dictionary
+            a = per_dev[str(device)] = DictArena(device)
+            a.pending = [(slot, s) for (dom, slot), s
+                         in self.id_to_str.items() if dom == domain]
+        a.upload()
+        return a
 
     def harvest(self, payload) -> int:
         """Drain the emit buffer after a batch. `payload` is the batch's

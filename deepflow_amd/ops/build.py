@@ -18,8 +18,8 @@ GPU_LIB = OPS_DIR / "libdfgpu.so"
 
 CPU_SOURCES = ["dfcpu.cpp", "agent_core.cpp", "otlp_conv.cpp",
                "recv_pump.cpp"]
-GPU_SOURCES = ["dfgpu.hip", "dfprofile.hip", "dftrace.hip", "dflog.hip",
-               "dfflow.hip", "dfdict.hip"]
+GPU_SOURCES = ["dfgpu.hip", "dfquery.hip", "dfprofile.hip", "dftrace.hip",
+               "dflog.hip", "dfflow.hip", "dfdict.hip"]
 
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 GFX_ARCH = os.environ.get("DF_GFX_ARCH", "gfx950")

@@ -3,8 +3,8 @@
 // DF-SQL `tag LIKE 'pat'` / `tag REGEXP 'pat'` on a SmartEncoding tag does
 // not look at rows: the pattern is matched once per distinct string of the
 // tag's dictionary domain and the result is a bitmap over dictionary ids.
-// The row filter (eval_terms in dfgpu.hip, OP_INSET / OP_NOT_INSET) is then
-// one bit test per row.
+// The row filter (eval_terms in dfquery.hip, OP_INSET / OP_NOT_INSET) is
+// then one bit test per row.
 //
 // The strings live in a device arena (store/dictionary.py DictArena): the
 // entries' bytes back to back, nothing between them, and three columns per

@@ -252,27 +252,17 @@ uint32_t df_flow_gv_n() { return GV_N; }
 uint32_t df_flow_rel_n() { return REL_N; }
 uint32_t df_flow_keys_per_row() { return FLOW_KEYS_PER_ROW; }
 
-// flat = 10 device pointers in FlowFlat order; idx_cap a power of two
-int df_flow_extract(const void* u64c, const void* u32c, const void* u8c,
-                    const void* str_rowref, const void* str_lens,
-                    const void* pool, uint64_t stride, uint32_t n_rows,
-                    uint32_t base_row, uint64_t time_start,
+// seg = a host SegView (dfseg.h); flat = 10 device pointers in FlowFlat
+// order; idx_cap a power of two
+int df_flow_extract(const void* seg, uint32_t base_row, uint64_t time_start,
                     uint64_t time_end, const uint64_t* flat, void* idx_keys,
                     void* idx_rows, void* drops, uint32_t idx_cap,
                     uint64_t stream) {
-    if (n_rows == 0) return 0;
-    SegView s{};
-    s.u64c = (const uint64_t*)u64c;
-    s.u32c = (const uint32_t*)u32c;
-    s.u8c = (const uint8_t*)u8c;
-    s.str_rowref = (const uint64_t*)str_rowref;
-    s.str_lens = (const int16_t*)str_lens;
-    s.pool = (const uint8_t*)pool;
-    s.stride = stride;
-    s.n_rows = n_rows;
+    SegView s = seg_view_load(seg);
+    if (s.n_rows == 0) return 0;
     FirstRowIdx ix{(uint64_t*)idx_keys, (uint32_t*)idx_rows,
                    (unsigned long long*)drops, idx_cap};
-    hipLaunchKernelGGL(k_flow_extract, dim3(grid_for(n_rows)), dim3(BLOCK),
+    hipLaunchKernelGGL(k_flow_extract, dim3(grid_for(s.n_rows)), dim3(BLOCK),
                        0, STREAM(stream), s, base_row, time_start, time_end,
                        flat_of(flat), ix);
     return (int)hipGetLastError();

@@ -1,5 +1,5 @@
 // Device hash helpers shared by the HIP translation units of libdfgpu.so
-// (dfgpu.hip, dfprofile.hip, dftrace.hip, dflog.hip, dfflow.hip), which get
+// (dfgpu.hip, dfquery.hip, dfprofile.hip, dftrace.hip, dflog.hip, dfflow.hip), which get
 // them through dftable.h and dfseg.h. Internal linkage: each unit gets its
 // own copy. DEV is defined here and nowhere else.
 #pragma once

@@ -1,9 +1,11 @@
 // Device view of one L7 segment and the rules for reading it that more
 // than one unit needs: the pooled strings of a row and the trace / span
-// keys. Trace-id filters (dfgpu.hip), the trace map (dftrace.hip) and flow
+// keys. Trace-id filters (dfquery.hip), the trace map (dftrace.hip) and flow
 // groups (dfflow.hip) agree with each other because they all take their
-// keys from here. Device-only, internal linkage (like dfhash.h).
+// keys from here. Internal linkage (like dfhash.h); device code, but for
+// the two host functions that carry the view across the C ABI.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 #include "l7_layout.h"
 #include "dfhash.h"
@@ -36,6 +38,31 @@ struct SegView {
     uint64_t stride;
     uint64_t n_rows;
 };
+
+// Across the C ABI the view travels as the address of a host struct of this
+// very layout (ops/gpu_ops.py SegViewC, filled by seg_view()). It is read
+// here, before the launch; kernels take the SegView by value.
+inline SegView seg_view_load(const void* seg) {
+    SegView s;
+    __builtin_memcpy(&s, seg, sizeof(SegView));
+    return s;
+}
+
+// offsetof every member, in declaration order: with sizeof, what a test
+// holds the Python mirror against (df_seg_view_offsets in dfquery.hip)
+constexpr uint32_t SEG_VIEW_MEMBERS = 15;
+inline void seg_view_offsets(uint32_t* out) {
+    const uint32_t offs[SEG_VIEW_MEMBERS] = {
+        offsetof(SegView, u64c), offsetof(SegView, u32c),
+        offsetof(SegView, u8c), offsetof(SegView, didc),
+        offsetof(SegView, kg_tk), offsetof(SegView, kg_tv),
+        offsetof(SegView, kg_mask), offsetof(SegView, attr_pool),
+        offsetof(SegView, attr_start), offsetof(SegView, attr_cnt),
+        offsetof(SegView, str_rowref), offsetof(SegView, str_lens),
+        offsetof(SegView, pool), offsetof(SegView, stride),
+        offsetof(SegView, n_rows)};
+    for (uint32_t i = 0; i < SEG_VIEW_MEMBERS; i++) out[i] = offs[i];
+}
 
 // pooled string `idx` of a row: pointer + length
 DEV const uint8_t* seg_pool_str(const SegView& s, uint64_t row, uint32_t idx,

@@ -19,16 +19,16 @@
 //    ids) are slot indices, so the units that start at `h & mask` and those
 //    that start at `mix64(h) & mask` must each stay as they are.
 //
-// Kept apart on purpose, all in dfgpu.hip unless named otherwise:
-//  - ru_claim_h verifies the raw key words behind the hash, publishes them
+// Kept apart on purpose:
+//  - ru_claim_h (dfgpu.hip) verifies the raw key words behind the hash, publishes them
 //    with a release store and gives up after RU_MAX_PROBES.
-//  - group_claim writes the raw key words inside its claim branch; routed
+//  - group_claim (dfquery.hip) writes the raw key words inside its claim branch; routed
 //    through `claimed` the flag stays live across the probe loop and costs
 //    k_query_agg and k_qpart_agg registers.
-//  - the LDS pre-aggregation tables (ru_pass, agg_vals_lds, the edge table
-//    of k_trace_fold in dftrace.hip) probe a fixed number of steps and
+//  - the LDS pre-aggregation tables (ru_pass in dfgpu.hip, agg_vals_lds in
+//    dfquery.hip, the edge table of k_trace_fold in dftrace.hip) probe a fixed number of steps and
 //    spill to the global table.
-// intern_probe_wave elects a lane and then calls intern_probe, which
+// intern_probe_wave (dfgpu.hip) elects a lane and then calls intern_probe, which
 // claims through table_claim.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -183,32 +183,36 @@ def pool_gather(payload: torch.Tensor, seg, pool_cols: torch.Tensor,
         "df_pool_gather")
 
 
-def _opt_ptr(seg, attr: str) -> int:
-    t = getattr(seg, attr, None)
-    return t.data_ptr() if t is not None else 0
+class SegViewC(ctypes.Structure):
+    """Host mirror of dfseg.h's SegView, member for member
+    (tests/test_query_kernels_gpu.py holds it against df_seg_view_size /
+    df_seg_view_offsets)."""
+    _fields_ = [(m, ctypes.c_void_p) for m in
+                ("u64c", "u32c", "u8c", "didc", "kg_tk", "kg_tv")] + \
+               [("kg_mask", ctypes.c_uint32)] + \
+               [(m, ctypes.c_void_p) for m in
+                ("attr_pool", "attr_start", "attr_cnt", "str_rowref",
+                 "str_lens", "pool")] + \
+               [("stride", ctypes.c_uint64), ("n_rows", ctypes.c_uint64)]
 
 
-def _kg_args(kg):
-    """KnowledgeGraph table pointers for the query-time join."""
-    if kg is None:
-        return 0, 0, 0
-    return kg.tkeys.data_ptr(), kg.tvals.data_ptr(), kg.tkeys.numel()
-
-
-def _seg_cols(seg):
-    return seg.u64.data_ptr(), seg.u32.data_ptr(), seg.u8.data_ptr()
-
-
-def _seg_pool(seg):
-    return (seg.str_rowref.data_ptr(), seg.str_lens.data_ptr(),
-            seg.pool.data_ptr(), seg.capacity, seg.n_rows)
-
-
-def _seg_args(seg, kg):
-    """The leading segment arguments of the three query entry points."""
-    return (*_seg_cols(seg), _opt_ptr(seg, "did"), *_kg_args(kg),
-            _opt_ptr(seg, "attr_pool"), _opt_ptr(seg, "attr_start"),
-            _opt_ptr(seg, "attr_cnt"), *_seg_pool(seg))
+def seg_view(seg, kg=None) -> SegViewC:
+    """The segment, and the KnowledgeGraph table of the query-time join, as
+    every entry point that reads one takes it. A tensor the segment does
+    not have stays null. The library reads the struct during the call, so
+    it only has to live that long."""
+    def ptr(attr):
+        t = getattr(seg, attr, None)
+        return t.data_ptr() if t is not None else None
+    v = SegViewC(u64c=ptr("u64"), u32c=ptr("u32"), u8c=ptr("u8"),
+                 didc=ptr("did"), attr_pool=ptr("attr_pool"),
+                 attr_start=ptr("attr_start"), attr_cnt=ptr("attr_cnt"),
+                 str_rowref=ptr("str_rowref"), str_lens=ptr("str_lens"),
+                 pool=ptr("pool"), stride=seg.capacity, n_rows=seg.n_rows)
+    if kg is not None:
+        v.kg_tk, v.kg_tv = kg.tkeys.data_ptr(), kg.tvals.data_ptr()
+        v.kg_mask = max(kg.tkeys.numel() - 1, 0)
+    return v
 
 
 def query_agg(seg, spec_bytes: bytes, base_row: int, n: int,
@@ -220,9 +224,8 @@ def query_agg(seg, spec_bytes: bytes, base_row: int, n: int,
     reported group, so a non-zero count means 'rerun with a larger
     table'."""
     lib = native.gpu()
-    buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
     native.check(lib.df_query_agg(
-        *_seg_args(seg, kg), ctypes.addressof(buf), n, base_row,
+        ctypes.byref(seg_view(seg, kg)), spec_bytes, n, base_row,
         gkeys.data_ptr(), graw.data_ptr(), gvals.data_ptr(), gkeys.numel(),
         overflow.data_ptr(), _stream()), "df_query_agg")
 
@@ -245,10 +248,8 @@ def query_uniq(seg, spec_bytes: bytes, uniq_bytes: bytes, base_row: int,
     cap = gkeys.numel()
     assert graw.numel() == cap * QMAX_KEYS and overflow.numel() >= 2
     assert guniq.numel() == cap * QMAX_UNIQ
-    buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
-    ubuf = ctypes.create_string_buffer(uniq_bytes, len(uniq_bytes))
     native.check(lib.df_query_uniq(
-        *_seg_args(seg, kg), ctypes.addressof(buf), ctypes.addressof(ubuf),
+        ctypes.byref(seg_view(seg, kg)), spec_bytes, uniq_bytes,
         n, base_row, gkeys.data_ptr(), graw.data_ptr(), gkeys.numel(),
         guniq.data_ptr(), pkeys.data_ptr(), pkeys.numel(),
         overflow.data_ptr(), 1 if use_filter else 0, _stream()),
@@ -267,9 +268,8 @@ def qpart_agg(seg, spec_bytes: bytes, base_row: int, n: int,
     counts/cursors: u32[256] (counts zeroed); row_scratch:
     u64[n * (n_keys+n_aggs)] payload staging; overflow: as in query_agg."""
     lib = native.gpu()
-    buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
     native.check(lib.df_qpart_agg(
-        *_seg_args(seg, kg), ctypes.addressof(buf), n, base_row,
+        ctypes.byref(seg_view(seg, kg)), spec_bytes, n, base_row,
         counts.data_ptr(), cursors.data_ptr(), row_scratch.data_ptr(),
         gkeys.data_ptr(), graw.data_ptr(), gvals.data_ptr(),
         gkeys.numel(), overflow.data_ptr(), _stream()), "df_qpart_agg")
@@ -279,9 +279,8 @@ def query_select(seg, spec_bytes: bytes, base_row: int, n: int,
                  out_rows: torch.Tensor, out_ctr: torch.Tensor,
                  kg=None) -> None:
     lib = native.gpu()
-    buf = ctypes.create_string_buffer(spec_bytes, len(spec_bytes))
     native.check(lib.df_query_select(
-        *_seg_args(seg, kg), ctypes.addressof(buf), n, base_row,
+        ctypes.byref(seg_view(seg, kg)), spec_bytes, n, base_row,
         out_rows.data_ptr(), out_ctr.data_ptr(), out_rows.numel(), _stream()),
         "df_query_select")
 
@@ -397,8 +396,7 @@ def trace_extract(seg, base_row: int, time_start: int, time_end: int,
                   ws) -> None:
     lib = native.gpu()
     native.check(lib.df_trace_extract(
-        *_seg_cols(seg), seg.did.data_ptr(), *_seg_pool(seg), base_row,
-        time_start, time_end,
+        ctypes.byref(seg_view(seg)), base_row, time_start, time_end,
         ws.flat_ptrs.ctypes.data, ws.idx_keys.data_ptr(),
         ws.idx_rows.data_ptr(), ws.drops.data_ptr(), ws.idx_cap,
         _stream()), "df_trace_extract")
@@ -438,7 +436,7 @@ def flow_extract(seg, base_row: int, time_start: int, time_end: int,
                  ws) -> None:
     lib = native.gpu()
     native.check(lib.df_flow_extract(
-        *_seg_cols(seg), *_seg_pool(seg), base_row, time_start, time_end,
+        ctypes.byref(seg_view(seg)), base_row, time_start, time_end,
         ws.flat_ptrs.ctypes.data,
         ws.idx_keys.data_ptr(), ws.idx_rows.data_ptr(),
         ws.drops.data_ptr(), ws.idx_cap, _stream()), "df_flow_extract")

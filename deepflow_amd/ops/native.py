@@ -134,31 +134,32 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_pool_lens.argtypes = [p, p, u32, u32, u64, u64, p, u64]
     lib.df_pool_gather.restype = ct.c_int
     lib.df_pool_gather.argtypes = [p, p, p, u32, u32, u64, u64, p, p, u64, p, p, u64, u64, u64]
+    # K7 query kernels (dfquery.hip). Their first argument, and that of
+    # df_trace_extract / df_flow_extract, is a gpu_ops.SegViewC
     lib.df_query_agg.restype = ct.c_int
-    lib.df_query_agg.argtypes = [p, p, p, p, p, p, u32, p, p, p, p, p, p,
-                                 u64, u64, p, u32, u64, p, p, p, u32, p,
-                                 u64]
+    lib.df_query_agg.argtypes = [p, p, u32, u64, p, p, p, u32, p, u64]
     lib.df_qpart_agg.restype = ct.c_int
-    lib.df_qpart_agg.argtypes = [p, p, p, p, p, p, u32, p, p, p, p, p, p,
-                                 u64, u64, p, u32, u64, p, p, p, p, p, p,
-                                 u32, p, u64]
+    lib.df_qpart_agg.argtypes = [p, p, u32, u64, p, p, p, p, p, p, u32, p,
+                                 u64]
     lib.df_query_select.restype = ct.c_int
-    lib.df_query_select.argtypes = [p, p, p, p, p, p, u32, p, p, p, p, p,
-                                    p, u64, u64, p, u32, u64, p, p, u32,
-                                    u64]
+    lib.df_query_select.argtypes = [p, p, u32, u64, p, p, u32, u64]
     lib.df_spec_sizes.restype = ct.c_int
     lib.df_spec_sizes.argtypes = [p, p, p, p]
-    # K15 distinct counts (k_query_uniq in dfgpu.hip)
+    lib.df_seg_view_size.restype = u32
+    lib.df_seg_view_size.argtypes = []
+    lib.df_seg_view_offsets.restype = None
+    lib.df_seg_view_offsets.argtypes = [ct.POINTER(u32)]
+    # K15 distinct counts (k_query_uniq in dfquery.hip)
     lib.df_query_uniq.restype = ct.c_int
-    lib.df_query_uniq.argtypes = [p, p, p, p, p, p, u32, p, p, p, p, p, p,
-                                  u64, u64, p, p, u32, u64, p, p, u32, p,
-                                  p, u32, p, u32, u64]
+    lib.df_query_uniq.argtypes = [p, p, p, u32, u64, p, p, u32, p, p, u32,
+                                  p, u32, u64]
     lib.df_uniq_spec_size.restype = u32
     lib.df_uniq_spec_size.argtypes = []
     lib.df_uniq_consts.restype = None
     lib.df_uniq_consts.argtypes = [ct.POINTER(u64), ct.POINTER(u64),
                                    ct.POINTER(u32), ct.POINTER(u32)]
-    # K16 set-membership filter ops and the dictionary walk (dfdict.hip)
+    # K16 set-membership filter ops (dfquery.hip) and the dictionary walk
+    # (dfdict.hip)
     lib.df_query_set_ops.restype = None
     lib.df_query_set_ops.argtypes = [ct.POINTER(u32)]
     lib.df_dict_re_limits.restype = None
@@ -190,8 +191,7 @@ def _decl_gpu(lib: ct.CDLL) -> None:
     lib.df_trace_max_hops.restype = u32
     lib.df_trace_max_hops.argtypes = []
     lib.df_trace_extract.restype = ct.c_int
-    lib.df_trace_extract.argtypes = [p, p, p, p, p, p, p, u64, u32, u32,
-                                     u64, u64, p, p, p, p, u32, u64]
+    lib.df_trace_extract.argtypes = [p, u32, u64, u64, p, p, p, p, u32, u64]
     lib.df_trace_link.restype = ct.c_int
     lib.df_trace_link.argtypes = [p, p, p, u32, u32, p, p, u64]
     lib.df_trace_depth.restype = ct.c_int
@@ -204,8 +204,7 @@ def _decl_gpu(lib: ct.CDLL) -> None:
         getattr(lib, getter).restype = u32
         getattr(lib, getter).argtypes = []
     lib.df_flow_extract.restype = ct.c_int
-    lib.df_flow_extract.argtypes = [p, p, p, p, p, p, u64, u32, u32, u64,
-                                    u64, p, p, p, p, u32, u64]
+    lib.df_flow_extract.argtypes = [p, u32, u64, u64, p, p, p, p, u32, u64]
     lib.df_flow_index.restype = ct.c_int
     lib.df_flow_index.argtypes = [p, p, p, p, u32, u32, u64]
     lib.df_flow_union.restype = ct.c_int

@@ -1,4 +1,4 @@
-"""QuerySpec ABI — ctypes mirror of dfgpu.hip's QTerm/QKey/QAgg/QuerySpec.
+"""QuerySpec ABI — ctypes mirror of dfquery.hip's QTerm/QKey/QAgg/QuerySpec.
 
 tests/test_query_spec.py validates sizeof against df_spec_sizes() so the two
 sides cannot drift silently.
@@ -16,7 +16,7 @@ QMAX_AGGS = 8
 QMAX_UNIQ = 4
 QMAX_UNIQ_ARGS = 4
 
-# source families (dfgpu.hip enum)
+# source families (dfquery.hip enum)
 SRC_U64 = 0
 SRC_U32 = 1
 SRC_U8 = 2
@@ -31,10 +31,10 @@ SRC_ATTR_MATCH = 9  # filter-only: attr name_id == v0 AND value_id == v1
 # zero binary cols fall back to the pooled-string hash (non-hex ids)
 SRC_TRACE128 = 10
 
-# seed for pooled-string filter hashing (twin: dfgpu.hip STR_FILTER_SEED)
+# seed for pooled-string filter hashing (twin: dfseg.h STR_FILTER_SEED)
 STR_FILTER_SEED = 0x5157A15E5EED
 
-# seed of the Uniq pair hash (twin: dfgpu.hip UNIQ_SEED; the formula is in
+# seed of the Uniq pair hash (twin: dfquery.hip UNIQ_SEED; the formula is in
 # k_query_uniq's comment)
 UNIQ_SEED = 0x13198A2E03707344
 # families src_value reads for a Uniq argument (SRC_ATTR_VAL is per-slot,

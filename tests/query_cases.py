@@ -7,7 +7,7 @@ from Term/Key/Agg directly, so every source family, filter op and launch
 shape is reachable on purpose.
 
 `ref_agg` / `ref_select` are a per-row pure-Python loop written from the
-semantics documented in ops/csrc/dfgpu.hip (src_value, eval_terms, the u64
+semantics documented in ops/csrc/dfquery.hip (src_value, eval_terms, the u64
 accumulators). They share no code with query/executor.py.
 """
 import copy
@@ -27,7 +27,7 @@ from deepflow_amd.store.segment import L7Segment
 
 M64 = (1 << 64) - 1
 M32 = 0xFFFFFFFF
-HASH_SEED = 0x243F6A8885A308D3      # k_query_agg's initial group hash
+HASH_SEED = 0x243F6A8885A308D3      # dfquery.hip GROUP_HASH_SEED
 HASH_ZERO_KEY = HASH_SEED           # mix64(seed ^ key) == mix64(0) == 0
 
 U64 = {c: i for i, c in enumerate(S.U64_COLS)}

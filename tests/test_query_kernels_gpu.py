@@ -2,12 +2,21 @@
 query_select) on the hand-built cases of query_cases.py, against its
 brute-force reference. The group-table size, base_row, n and the kernel
 taken are chosen by the test. Everything is integer: every comparison is
-exact, as sets/dicts (slot and emit order are undefined)."""
+exact, as sets/dicts (slot and emit order are undefined).
+
+Below them: what the four query entry points (the three and
+gpu_ops.query_uniq) share across the C ABI. The SegView mirror against the
+library's layout, the spec checks that come before any launch, and the one
+group hash of every path."""
+import ctypes as ct
+
 import numpy as np
 import pytest
 import torch
 
 import query_cases as QC
+import uniq_cases as UC
+from deepflow_amd.ops.ref import mix64
 from deepflow_amd.query import spec as Q
 
 pytestmark = pytest.mark.gpu
@@ -340,3 +349,170 @@ def test_execute_agg_gpu_grows_the_group_table(monkeypatch):
     monkeypatch.setattr(ex, "GROUP_CAP_MAX", 64)
     with pytest.raises(RuntimeError, match="more than 64 groups"):
         ex.execute_agg_gpu(case.plan, dsegs)
+
+
+# ------------------------------------------------- the segment view ABI
+
+def test_seg_view_mirror_matches_the_library():
+    """sizeof and every member offset of gpu_ops.SegViewC are the
+    library's SegView's. No kernel runs."""
+    from deepflow_amd.ops import gpu_ops, native
+    lib = native.gpu()
+    mirror = gpu_ops.SegViewC
+    names = [name for name, _ in mirror._fields_]
+    # room to spare behind the mirror's members: a member the library has
+    # and the mirror lacks lands on a guard word instead of past the array
+    guard = 0xFFFFFFFF
+    offs = (ct.c_uint32 * (len(names) + 8))(*[guard] * (len(names) + 8))
+    lib.df_seg_view_offsets(offs)
+    assert ct.sizeof(mirror) == lib.df_seg_view_size()
+    assert list(offs[:len(names)]) == [getattr(mirror, n).offset
+                                       for n in names]
+    assert list(offs[len(names):]) == [guard] * 8
+
+
+# ------------------------------------------- spec checks before a launch
+
+ENTRIES = ["agg", "qpart", "uniq", "select"]
+UNTOUCHED = 5
+HIP_INVALID_VALUE = r"HIP error 1 in "      # not 9, invalid configuration
+
+
+def call_entry(entry, seg, spec, uspec, n, cap):
+    """One call of a query entry point with `cap`-slot tables.
+    -> every device tensor it could write, each filled with UNTOUCHED."""
+    from deepflow_amd.ops import gpu_ops
+
+    def t(*shape, dtype=torch.int64):
+        return torch.full(shape, UNTOUCHED, dtype=dtype, device="cuda")
+    gkeys, graw, gvals = t(cap), t(cap, Q.QMAX_KEYS), t(cap, Q.QMAX_AGGS)
+    ovf = t(2, dtype=torch.int32)
+    if entry == "agg":
+        out = [gkeys, graw, gvals, ovf]
+        gpu_ops.query_agg(seg, spec, 0, n, gkeys, graw, gvals, overflow=ovf)
+    elif entry == "qpart":
+        counts, cursors = t(256, dtype=torch.int32), t(256, dtype=torch.int32)
+        scratch = t(64)
+        out = [gkeys, graw, gvals, ovf, counts, cursors, scratch]
+        gpu_ops.qpart_agg(seg, spec, 0, n, counts, cursors, scratch, gkeys,
+                          graw, gvals, overflow=ovf)
+    elif entry == "uniq":
+        guniq, pkeys = t(cap, Q.QMAX_UNIQ), t(1024)
+        out = [gkeys, graw, guniq, pkeys, ovf]
+        gpu_ops.query_uniq(seg, spec, uspec, 0, n, gkeys, graw, guniq, pkeys,
+                           overflow=ovf)
+    else:
+        rows, ctr = t(16), t(1, dtype=torch.int32)
+        out = [rows, ctr]
+        gpu_ops.query_select(seg, spec, 0, n, rows, ctr)
+    torch.cuda.synchronize()
+    return out
+
+
+@pytest.mark.parametrize("entry", ENTRIES)
+def test_bad_specs_are_refused_before_any_launch(entry):
+    """n = 0 throughout, so a check that is missing cannot put a malformed
+    spec in front of a kernel: it shows as a call that does not raise."""
+    dseg = QC.to_device(QC.geometry_segment())
+    plan = UC.uplan([[UC.RRT]], [UC.K_PROTO])
+    spec, uspec = plan.to_bytes(), plan.uniq_to_bytes()
+    # well-formed and empty: a clean return, nothing written
+    for buf in call_entry(entry, dseg, spec, uspec, 0, 1024):
+        assert bool((buf == UNTOUCHED).all())
+
+    def with_count(field, value):
+        bad = bytearray(spec)
+        off = getattr(Q.QuerySpecC, field).offset
+        bad[off:off + 4] = value.to_bytes(4, "little")
+        return bytes(bad)
+    bad_calls = [(with_count("n_terms", Q.QMAX_TERMS + 1), 1024),
+                 (with_count("n_keys", Q.QMAX_KEYS + 1), 1024),
+                 (with_count("n_aggs", Q.QMAX_AGGS + 1), 1024)]
+    if entry != "select":           # the one entry point without a table
+        bad_calls.append((spec, 768))
+    for bad_spec, cap in bad_calls:
+        with pytest.raises(RuntimeError, match=HIP_INVALID_VALUE):
+            call_entry(entry, dseg, bad_spec, uspec, 0, cap)
+
+
+# ------------------------------------------------ one hash on every path
+
+def hash_paths_case():
+    """Two segments of 300 rows (one full block and a partial one) over 40
+    tuples of QMAX_KEYS keys. One tuple is hash_zero_case's key completed
+    to four so that its hash is still 0 before the 0 -> 1 rule: the last
+    key is a u64 column, set to undo what the three before it left."""
+    rng = np.random.default_rng(1615)
+    keys = [QC.Key(Q.SRC_U64, QC.U64["flow_id"]),
+            QC.Key(Q.SRC_U32, QC.U32["server_port"]),
+            QC.Key(Q.SRC_U8, QC.U8["l7_protocol"]),
+            QC.Key(Q.SRC_U64, QC.U64["syscall_trace_id_request"])]
+    assert len(keys) == Q.QMAX_KEYS
+    tuples = {(int(rng.integers(1, 1 << 62)), int(rng.integers(0, 1 << 16)),
+               int(rng.integers(0, 4)), int(rng.integers(0, 1 << 62)))
+              for _ in range(39)}
+    h = QC.HASH_SEED
+    for k, v in enumerate((QC.HASH_ZERO_KEY, 443, 2)):
+        h = mix64(h ^ v ^ (k << 56))
+    zero = (QC.HASH_ZERO_KEY, 443, 2, h ^ (3 << 56))
+    assert QC.group_hash(zero) == 1 and len(tuples | {zero}) == 40
+    tuples = np.array(sorted(tuples | {zero}), dtype=np.uint64)
+    rrt = QC.U64["rrt"]
+    plan = UC.uplan([[UC.RRT]], keys,
+                    extra_aggs=[QC.COUNT, QC.Agg(Q.AGGOP_SUM, Q.SRC_U64, rrt),
+                                QC.Agg(Q.AGGOP_MIN, Q.SRC_U64, rrt),
+                                QC.Agg(Q.AGGOP_MAX, Q.SRC_U64, rrt)])
+    segs = []
+    for _ in range(2):
+        # every tuple at least once per segment, the rest at random
+        pick = tuples[np.concatenate([rng.permutation(40),
+                                      rng.integers(0, 40, 260)])]
+        seg = QC.new_segment(300)
+        QC.set_u64(seg, "flow_id", pick[:, 0])
+        QC.set_u32(seg, "server_port", pick[:, 1])
+        QC.set_u8(seg, "l7_protocol", pick[:, 2])
+        QC.set_u64(seg, "syscall_trace_id_request", pick[:, 3])
+        QC.set_u64(seg, "rrt", rng.integers(1, 12, 300))
+        segs.append(seg)
+    return plan, segs, zero
+
+
+def test_every_path_names_a_group_by_one_hash():
+    """Segment A through query_agg, segment B through qpart_agg, both
+    through query_uniq, all into one 1024-slot table. A path that hashed a
+    tuple differently would give it a second slot, or count its distinct
+    values against another group's."""
+    from deepflow_amd.ops import gpu_ops
+    from deepflow_amd.query.executor import execute_agg_cpu
+    plan, segs, zero = hash_paths_case()
+    want = {tuple(g["key"]): (g["agg"], g["uniq"])
+            for g in execute_agg_cpu(plan, segs)}
+    assert len(want) == 40 and zero in want
+    dsegs = [QC.to_device(s) for s in segs]
+    table = run_agg("direct", dsegs[0], plan, cap=1024)
+    table = run_agg("qpart", dsegs[1], plan, table=table)
+    gkeys, graw, gvals, overflow = table
+    guniq = torch.zeros((1024, Q.QMAX_UNIQ), dtype=torch.int64,
+                        device="cuda")
+    pkeys = torch.zeros(1 << 12, dtype=torch.int64, device="cuda")
+    lost = torch.zeros(2, dtype=torch.int32, device="cuda")
+    for dseg in dsegs:
+        gpu_ops.query_uniq(dseg, plan.to_bytes(), plan.uniq_to_bytes(), 0,
+                           dseg.n_rows, gkeys, graw, guniq, pkeys,
+                           overflow=lost)
+    torch.cuda.synchronize()
+    assert lost_rows(table) == 0 and lost.tolist() == [0, 0]
+    live = torch.nonzero(gkeys != 0).flatten().tolist()
+    assert len(live) == 40          # every tuple owns exactly one slot
+    assert int(guniq[gkeys == 0].abs().sum().item()) == 0
+    raw = graw.cpu().numpy().view(np.uint64)
+    vals = gvals.cpu().numpy().view(np.uint64)
+    seen = set()
+    for slot in live:
+        key = tuple(raw[slot].tolist())
+        seen.add(key)
+        assert int(gkeys[slot].item()) & QC.M64 == QC.group_hash(key)
+        aggs, uniq = want[key]
+        assert vals[slot, :len(plan.aggs)].tolist() == aggs, key
+        assert guniq[slot, :len(plan.uniqs)].tolist() == uniq, key
+    assert seen == set(want)

@@ -3,7 +3,7 @@ distinct-count aggregates (Uniq / UniqExact), shared by test_uniq_cpu.py
 and test_uniq_gpu.py.
 
 `ref_uniq` is a per-row pure-Python loop over the semantics documented at
-k_query_uniq in ops/csrc/dfgpu.hip; it shares no code with
+k_query_uniq in ops/csrc/dfquery.hip; it shares no code with
 query/executor.py (it reads rows through query_cases.ref_value /
 ref_match). `pair_hash` rebuilds the documented formula, the way
 query_cases.group_hash rebuilds the group hash.
@@ -21,7 +21,7 @@ from deepflow_amd.store import l7_schema as S
 M64 = QC.M64
 U64, U32, U8 = QC.U64, QC.U32, QC.U8
 
-# twins of dfgpu.hip UNIQ_SEED / UNIQ_ITEM_MUL / UNIQ_FILTER_SLOTS /
+# twins of dfquery.hip UNIQ_SEED / UNIQ_ITEM_MUL / UNIQ_FILTER_SLOTS /
 # UNIQ_FILTER_SHIFT (test_uniq_gpu.py compares them with df_uniq_consts)
 UNIQ_SEED = 0x13198A2E03707344
 UNIQ_ITEM_MUL = 0x9E3779B97F4A7C15

@@ -17,7 +17,7 @@ CPU_LIB = OPS_DIR / "libdfcpu.so"
 GPU_LIB = OPS_DIR / "libdfgpu.so"
 
 CPU_SOURCES = ["dfcpu.cpp", "agent_core.cpp", "otlp_conv.cpp",
-               "recv_pump.cpp"]
+               "recv_pump.cpp", "decode_host.cpp"]
 GPU_SOURCES = ["dfgpu.hip", "dfquery.hip", "dfprofile.hip", "dftrace.hip",
                "dflog.hip", "dfflow.hip", "dfdict.hip"]
 

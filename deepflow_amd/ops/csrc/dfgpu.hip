@@ -21,104 +21,16 @@
 // Build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC
 #include <hip/hip_runtime.h>
 #include "dftable.h"
+#include "l7_decode.h"
+#include "l4_decode.h"
 
 namespace {
 
-// Word-buffered byte stream: protobuf parsing is byte-granular and
-// sequential per record; buffering an aligned u64 per 8 bytes turns 8
-// byte-loads into one dwordx2 load (the payload tensor base is
-// 256B-aligned, so aligned word indexing is safe).
-struct ByteStream {
-    const uint64_t* w;
-    uint64_t cur;
-    uint32_t wpos;
-    DEV void init(const uint8_t* base) {
-        w = (const uint64_t*)base;
-        wpos = 0xFFFFFFFFu;
-        cur = 0;
-    }
-    DEV uint8_t get(uint32_t i) {
-        uint32_t wp = i >> 3;
-        if (wp != wpos) {
-            wpos = wp;
-            cur = w[wp];
-        }
-        return (uint8_t)(cur >> ((i & 7) * 8));
-    }
-};
-
-DEV uint64_t rd_varint(ByteStream& bs, uint32_t& pos, uint32_t end) {
-    uint64_t v = 0;
-    int sh = 0;
-    while (pos < end) {
-        uint8_t b = bs.get(pos++);
-        v |= (uint64_t)(b & 0x7F) << sh;
-        if (!(b & 0x80)) break;
-        sh += 7;
-        if (sh >= 70) break;
-    }
-    return v;
-}
-
-DEV void skip_field(ByteStream& bs, uint32_t& pos, uint32_t end, uint32_t wt) {
-    switch (wt) {
-        case 0: rd_varint(bs, pos, end); break;
-        case 1: pos += 8; break;
-        case 2: { uint64_t ln = rd_varint(bs, pos, end); pos += (uint32_t)ln; } break;
-        case 5: pos += 4; break;
-        default: pos = end; break;  // malformed
-    }
-}
-
-DEV uint64_t rd_varint(const uint8_t* p, uint32_t& pos, uint32_t end) {
-    uint64_t v = 0;
-    int sh = 0;
-    while (pos < end) {
-        uint8_t b = p[pos++];
-        v |= (uint64_t)(b & 0x7F) << sh;
-        if (!(b & 0x80)) break;
-        sh += 7;
-        if (sh >= 70) break;
-    }
-    return v;
-}
-
-DEV void skip_field(const uint8_t* p, uint32_t& pos, uint32_t end, uint32_t wt) {
-    switch (wt) {
-        case 0: rd_varint(p, pos, end); break;
-        case 1: pos += 8; break;
-        case 2: { uint64_t ln = rd_varint(p, pos, end); pos += (uint32_t)ln; } break;
-        case 5: pos += 4; break;
-        default: pos = end; break;  // malformed
-    }
-}
-
-// parse 16 hex chars at pos -> u64; false on non-hex (parser: dfhash.h)
-DEV bool hex_parse64(ByteStream& bs, uint32_t pos, uint64_t& out) {
-    return hex_parse64_with(
-        [&](uint32_t i) -> uint8_t { return bs.get(pos + i); }, out);
-}
-
 // ----------------------------------------------------------------------
-// K1: AppProtoLogsData protobuf decode, thread-per-record.
+// K1 / K1b: protobuf decode, thread-per-record. The per-record parsers
+// (and the malformed-record contract) are in l7_decode.h / l4_decode.h,
+// which also compile for the host.
 // ----------------------------------------------------------------------
-
-struct L7Cols {
-    uint64_t* u64c;       // [L7_U64_N, stride]
-    uint32_t* u32c;       // [L7_U32_N, stride]
-    uint8_t* u8c;         // [L7_U8_N, stride]
-    uint64_t* strc;       // SCRATCH [L7_STR_N, scratch_stride], row = rid
-    uint64_t* attrc;      // SCRATCH [2*L7_MAX_ATTRS, scratch_stride]
-    uint8_t* attr_cnt;    // [stride] (segment)
-    uint64_t stride;
-    uint64_t base_row;
-    uint64_t scratch_stride;
-};
-
-#define W64(c, v) cols.u64c[(uint64_t)(c) * cols.stride + row] = (v)
-#define W32(c, v) cols.u32c[(uint64_t)(c) * cols.stride + row] = (uint32_t)(v)
-#define W8(c, v)  cols.u8c[(uint64_t)(c) * cols.stride + row] = (uint8_t)(v)
-#define WSTR(c, off, len) cols.strc[(uint64_t)(c) * cols.scratch_stride + rid] = STR_REF_PACK(off, len)
 
 __global__ void k_decode_l7(const uint8_t* __restrict__ payload,
                             const uint32_t* __restrict__ offs,
@@ -126,249 +38,10 @@ __global__ void k_decode_l7(const uint8_t* __restrict__ payload,
                             uint32_t n, L7Cols cols) {
     uint32_t rid = blockIdx.x * blockDim.x + threadIdx.x;
     if (rid >= n) return;
-    uint64_t row = cols.base_row + rid;
-    uint32_t pos = offs[rid];
     ByteStream bs;
     bs.init(payload);
-    uint32_t end = pos + lens[rid];
-    uint32_t n_names = 0, n_vals = 0;
-
-    while (pos < end) {
-        uint64_t key = rd_varint(bs, pos, end);
-        uint32_t num = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
-        if (wt == 0) {
-            uint64_t v = rd_varint(bs, pos, end);
-            switch (num) {
-                case 9: W32(L7_U32_REQ_LEN, v); break;
-                case 10: W32(L7_U32_RESP_LEN, v); break;
-                case 17: W8(L7_U8_DIR_SCORE, v); break;
-                case 18: W32(L7_U32_FLAGS, v); break;
-                case 19: W32(L7_U32_CAP_REQ_BYTE, v); break;
-                case 20: W32(L7_U32_CAP_RESP_BYTE, v); break;
-                default: break;
-            }
-        } else if (wt == 2) {
-            uint32_t ln = (uint32_t)rd_varint(bs, pos, end);
-            uint32_t sub = pos, send = pos + ln;
-            pos = send;
-            switch (num) {
-                case 1: {  // AppProtoLogsBaseInfo
-                    uint32_t p2 = sub;
-                    while (p2 < send) {
-                        uint64_t k2 = rd_varint(bs, p2, send);
-                        uint32_t n2 = (uint32_t)(k2 >> 3), w2 = (uint32_t)(k2 & 7);
-                        if (w2 == 0) {
-                            uint64_t v = rd_varint(bs, p2, send);
-                            switch (n2) {
-                                case 1: W64(L7_U64_START_TIME, v); break;
-                                case 2: W64(L7_U64_END_TIME, v); break;
-                                case 3: W64(L7_U64_FLOW_ID, v); break;
-                                case 5: W32(L7_U32_VTAP_ID, v); break;
-                                case 6: W8(L7_U8_TAP_TYPE, v); break;
-                                case 7: W8(L7_U8_IS_IPV6, v); break;
-                                case 8: W8(L7_U8_TAP_SIDE, v); break;
-                                case 12: W32(L7_U32_IP4_0, v); break;
-                                case 13: W32(L7_U32_IP4_1, v); break;
-                                case 16: W32(L7_U32_EPC_0, v); break;
-                                case 17: W32(L7_U32_EPC_1, v); break;
-                                case 18: W32(L7_U32_PORT_0, v); break;
-                                case 19: W32(L7_U32_PORT_1, v); break;
-                                case 20: W8(L7_U8_PROTOCOL, v); break;
-                                case 23: W32(L7_U32_REQ_TCP_SEQ, v); break;
-                                case 24: W32(L7_U32_RESP_TCP_SEQ, v); break;
-                                case 25: W32(L7_U32_PID_0, v); break;
-                                case 26: W32(L7_U32_PID_1, v); break;
-                                case 29: W64(L7_U64_SYSCALL_REQ, v); break;
-                                case 30: W64(L7_U64_SYSCALL_RESP, v); break;
-                                case 35: W32(L7_U32_GPID_0, v); break;
-                                case 36: W32(L7_U32_GPID_1, v); break;
-                                case 41: W32(L7_U32_POD_0, v); break;
-                                case 42: W32(L7_U32_POD_1, v); break;
-                                case 43: W32(L7_U32_BIZ_TYPE, v); break;
-                                default: break;
-                            }
-                        } else if (w2 == 2) {
-                            uint32_t l3 = (uint32_t)rd_varint(bs, p2, send);
-                            uint32_t s3 = p2, e3 = p2 + l3;
-                            p2 = e3;
-                            if (n2 == 9) {  // AppProtoHead
-                                uint32_t p3 = s3;
-                                while (p3 < e3) {
-                                    uint64_t k3 = rd_varint(bs, p3, e3);
-                                    if ((k3 & 7) == 0) {
-                                        uint64_t v = rd_varint(bs, p3, e3);
-                                        switch ((uint32_t)(k3 >> 3)) {
-                                            case 1: W8(L7_U8_L7_PROTOCOL, v); break;
-                                            case 2: W8(L7_U8_MSG_TYPE, v); break;
-                                            case 5: W64(L7_U64_RRT, v); break;
-                                            default: break;
-                                        }
-                                    } else {
-                                        uint32_t w3 = (uint32_t)(k3 & 7);
-                                        skip_field(bs, p3, e3, w3);
-                                    }
-                                }
-                            } else if (n2 == 27) {
-                                WSTR(L7_STR_PKNAME_0, s3, l3);
-                            } else if (n2 == 28) {
-                                WSTR(L7_STR_PKNAME_1, s3, l3);
-                            } else if (n2 == 14) {   // ip6_src (16 raw bytes,
-                                WSTR(L7_STR_IP6_0, s3, l3);  // pooled)
-                            } else if (n2 == 15) {   // ip6_dst
-                                WSTR(L7_STR_IP6_1, s3, l3);
-                            }
-                        } else {
-                            skip_field(bs, p2, send, w2);
-                        }
-                    }
-                    break;
-                }
-                case 11: {  // L7Request
-                    uint32_t p2 = sub;
-                    while (p2 < send) {
-                        uint64_t k2 = rd_varint(bs, p2, send);
-                        uint32_t n2 = (uint32_t)(k2 >> 3), w2 = (uint32_t)(k2 & 7);
-                        if (w2 == 2) {
-                            uint32_t l3 = (uint32_t)rd_varint(bs, p2, send);
-                            switch (n2) {
-                                case 1: WSTR(L7_STR_REQ_TYPE, p2, l3); break;
-                                case 2: WSTR(L7_STR_DOMAIN, p2, l3); break;
-                                case 3: WSTR(L7_STR_RESOURCE, p2, l3); break;
-                                case 4: WSTR(L7_STR_ENDPOINT, p2, l3); break;
-                                default: break;
-                            }
-                            p2 += l3;
-                        } else {
-                            skip_field(bs, p2, send, w2);
-                        }
-                    }
-                    break;
-                }
-                case 12: {  // L7Response
-                    uint32_t p2 = sub;
-                    while (p2 < send) {
-                        uint64_t k2 = rd_varint(bs, p2, send);
-                        uint32_t n2 = (uint32_t)(k2 >> 3), w2 = (uint32_t)(k2 & 7);
-                        if (w2 == 0) {
-                            uint64_t v = rd_varint(bs, p2, send);
-                            if (n2 == 1) W8(L7_U8_STATUS, v);
-                            else if (n2 == 2) W32(L7_U32_CODE, v);
-                        } else if (w2 == 2) {
-                            uint32_t l3 = (uint32_t)rd_varint(bs, p2, send);
-                            if (n2 == 3) WSTR(L7_STR_EXCEPTION, p2, l3);
-                            else if (n2 == 4) WSTR(L7_STR_RESULT, p2, l3);
-                            p2 += l3;
-                        } else {
-                            skip_field(bs, p2, send, w2);
-                        }
-                    }
-                    break;
-                }
-                case 13: WSTR(L7_STR_VERSION, sub, ln); break;
-                case 14: {  // TraceInfo: hex ids transcode to binary
-                    // columns (SmartEncoding: a 32-hex trace id stores as
-                    // 16 B of u64s, not 48 B of pool+len); non-hex ids
-                    // fall back to the pool columns
-                    uint32_t p2 = sub;
-                    while (p2 < send) {
-                        uint64_t k2 = rd_varint(bs, p2, send);
-                        uint32_t n2 = (uint32_t)(k2 >> 3), w2 = (uint32_t)(k2 & 7);
-                        if (w2 == 2) {
-                            uint32_t l3 = (uint32_t)rd_varint(bs, p2, send);
-                            if (n2 == 1) {
-                                uint64_t hi, lo;
-                                if (l3 == 32 &&
-                                    hex_parse64(bs, p2, hi) &&
-                                    hex_parse64(bs, p2 + 16, lo)) {
-                                    W64(L7_U64_TRACE_HI, hi);
-                                    W64(L7_U64_TRACE_LO, lo);
-                                } else {
-                                    WSTR(L7_STR_TRACE_ID, p2, l3);
-                                }
-                            } else if (n2 == 2) {
-                                uint64_t sv;
-                                if (l3 == 16 && hex_parse64(bs, p2, sv)) {
-                                    W64(L7_U64_SPAN_ID_B, sv);
-                                } else {
-                                    WSTR(L7_STR_SPAN_ID, p2, l3);
-                                }
-                            } else if (n2 == 3) {
-                                WSTR(L7_STR_PARENT_SPAN_ID, p2, l3);
-                            }
-                            p2 += l3;
-                        } else {
-                            skip_field(bs, p2, send, w2);
-                        }
-                    }
-                    break;
-                }
-                case 15: {  // ExtendedInfo
-                    uint32_t p2 = sub;
-                    while (p2 < send) {
-                        uint64_t k2 = rd_varint(bs, p2, send);
-                        uint32_t n2 = (uint32_t)(k2 >> 3), w2 = (uint32_t)(k2 & 7);
-                        if (w2 == 0) {
-                            uint64_t v = rd_varint(bs, p2, send);
-                            if (n2 == 3) W32(L7_U32_REQUEST_ID, v);
-                        } else if (w2 == 2) {
-                            uint32_t l3 = (uint32_t)rd_varint(bs, p2, send);
-                            switch (n2) {
-                                case 1: WSTR(L7_STR_SERVICE_NAME, p2, l3); break;
-                                case 4: WSTR(L7_STR_XREQ_0, p2, l3); break;
-                                case 6: WSTR(L7_STR_UA, p2, l3); break;
-                                case 7: WSTR(L7_STR_REFERER, p2, l3); break;
-                                case 10: WSTR(L7_STR_XREQ_1, p2, l3); break;
-                                case 16:
-                                    if (n_names < L7_MAX_ATTRS)
-                                        cols.attrc[(uint64_t)n_names * cols.scratch_stride + rid] =
-                                            STR_REF_PACK(p2, l3);
-                                    n_names++;
-                                    break;
-                                case 17:
-                                    if (n_vals < L7_MAX_ATTRS)
-                                        cols.attrc[(uint64_t)(L7_MAX_ATTRS + n_vals) * cols.scratch_stride + rid] =
-                                            STR_REF_PACK(p2, l3);
-                                    n_vals++;
-                                    break;
-                                default: break;
-                            }
-                            p2 += l3;
-                        } else {
-                            skip_field(bs, p2, send, w2);
-                        }
-                    }
-                    break;
-                }
-                case 21: WSTR(L7_STR_BIZ_CODE, sub, ln); break;
-                default: break;
-            }
-        } else {
-            skip_field(bs, pos, end, wt);
-        }
-    }
-    uint32_t na = n_names < n_vals ? n_names : n_vals;
-    cols.attr_cnt[row] = (uint8_t)(na > L7_MAX_ATTRS ? L7_MAX_ATTRS : na);
+    decode_l7_record(bs, offs[rid], lens[rid], rid, cols);
 }
-
-// ----------------------------------------------------------------------
-// K1b: TaggedFlow (L4 flow log) protobuf decode, thread-per-record.
-// Wire schema: message/flow_log.proto:14-120; columns: l4_layout.h.
-// ----------------------------------------------------------------------
-#include "l4_layout.h"
-
-struct L4Cols {
-    uint64_t* u64c;
-    uint32_t* u32c;
-    uint8_t* u8c;
-    uint64_t* strc;   // SCRATCH [L4_STR_N, scratch_stride], row = rid
-    uint64_t stride;
-    uint64_t base_row;
-    uint64_t scratch_stride;
-};
-
-#define L4W64(c, v) cols.u64c[(uint64_t)(c) * cols.stride + row] = (v)
-#define L4W32(c, v) cols.u32c[(uint64_t)(c) * cols.stride + row] = (uint32_t)(v)
-#define L4W8(c, v)  cols.u8c[(uint64_t)(c) * cols.stride + row] = (uint8_t)(v)
 
 __global__ void k_decode_l4(const uint8_t* __restrict__ payload,
                             const uint32_t* __restrict__ offs,
@@ -376,216 +49,9 @@ __global__ void k_decode_l4(const uint8_t* __restrict__ payload,
                             uint32_t n, L4Cols cols) {
     uint32_t rid = blockIdx.x * blockDim.x + threadIdx.x;
     if (rid >= n) return;
-    uint64_t row = cols.base_row + rid;
-    uint32_t pos = offs[rid];
     ByteStream bs;
     bs.init(payload);
-    uint32_t end = pos + lens[rid];
-    // locate flow submessage (TaggedFlow field 1)
-    while (pos < end) {
-        uint64_t key = rd_varint(bs, pos, end);
-        uint32_t num = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
-        if (num == 1 && wt == 2) {
-            uint32_t ln = (uint32_t)rd_varint(bs, pos, end);
-            end = pos + ln;  // narrow to Flow
-            break;
-        }
-        skip_field(bs, pos, end, wt);
-    }
-    while (pos < end) {
-        uint64_t key = rd_varint(bs, pos, end);
-        uint32_t num = (uint32_t)(key >> 3), wt = (uint32_t)(key & 7);
-        if (wt == 0) {
-            uint64_t v = rd_varint(bs, pos, end);
-            switch (num) {
-                case 5: L4W64(L4_U64_FLOW_ID, v); break;
-                case 6: L4W64(L4_U64_START_TIME, v); break;
-                case 7: L4W64(L4_U64_END_TIME, v); break;
-                case 8: L4W64(L4_U64_DURATION, v); break;
-                case 10: L4W32(L4_U32_VLAN, v); break;
-                case 11: L4W32(L4_U32_ETH_TYPE, v); break;
-                case 14: L4W8(L4_U8_CLOSE_TYPE, v); break;
-                case 15: L4W8(L4_U8_SIGNAL_SOURCE, v); break;
-                case 16: L4W8(L4_U8_IS_ACTIVE_SERVICE, v); break;
-                case 18: L4W8(L4_U8_IS_NEW_FLOW, v); break;
-                case 19: L4W8(L4_U8_TAP_SIDE, v); break;
-                case 25: L4W8(L4_U8_DIRECTION_SCORE, v); break;
-                default: break;
-            }
-        } else if (wt == 2) {
-            uint32_t ln = (uint32_t)rd_varint(bs, pos, end);
-            uint32_t sub = pos, send = pos + ln;
-            pos = send;
-            switch (num) {
-                case 1: {  // FlowKey
-                    uint32_t p2 = sub;
-                    while (p2 < send) {
-                        uint64_t k2 = rd_varint(bs, p2, send);
-                        uint32_t n2 = (uint32_t)(k2 >> 3), w2 = (uint32_t)(k2 & 7);
-                        if (w2 == 0) {
-                            uint64_t v = rd_varint(bs, p2, send);
-                            switch (n2) {
-                                case 1: L4W32(L4_U32_VTAP_ID, v); break;
-                                case 2: L4W8(L4_U8_TAP_TYPE, v); break;
-                                case 4: L4W64(L4_U64_MAC_SRC, v); break;
-                                case 5: L4W64(L4_U64_MAC_DST, v); break;
-                                case 6: L4W32(L4_U32_IP4_0, v); break;
-                                case 7: L4W32(L4_U32_IP4_1, v); break;
-                                case 10: L4W32(L4_U32_PORT_SRC, v); break;
-                                case 11: L4W32(L4_U32_PORT_DST, v); break;
-                                case 12: L4W8(L4_U8_PROTOCOL, v); break;
-                                default: break;
-                            }
-                        } else if (w2 == 2 && (n2 == 8 || n2 == 9)) {
-                            // ip6_src/dst: raw 16 bytes into the str pool
-                            uint32_t l3 = (uint32_t)rd_varint(bs, p2, send);
-                            cols.strc[(uint64_t)(n2 == 8 ? L4_STR_IP6_0
-                                                         : L4_STR_IP6_1) *
-                                      cols.scratch_stride + rid] =
-                                STR_REF_PACK(p2, l3);
-                            p2 += l3;
-                        } else {
-                            skip_field(bs, p2, send, w2);
-                        }
-                    }
-                    break;
-                }
-                case 24: {  // acl_gids (packed repeated u32): keep first
-                    uint32_t p2 = sub;
-                    if (p2 < send) {
-                        uint64_t v = rd_varint(bs, p2, send);
-                        L4W32(L4_U32_ACL_GID, v);
-                    }
-                    break;
-                }
-                case 2: case 3: {  // FlowMetricsPeer src/dst
-                    bool tx = num == 2;
-                    uint32_t p2 = sub;
-                    while (p2 < send) {
-                        uint64_t k2 = rd_varint(bs, p2, send);
-                        uint32_t n2 = (uint32_t)(k2 >> 3), w2 = (uint32_t)(k2 & 7);
-                        if (w2 == 0) {
-                            uint64_t v = rd_varint(bs, p2, send);
-                            switch (n2) {
-                                case 1: L4W64(tx ? L4_U64_BYTE_TX : L4_U64_BYTE_RX, v); break;
-                                case 2: L4W64(tx ? L4_U64_L3_BYTE_TX : L4_U64_L3_BYTE_RX, v); break;
-                                case 3: L4W64(tx ? L4_U64_L4_BYTE_TX : L4_U64_L4_BYTE_RX, v); break;
-                                case 4: L4W64(tx ? L4_U64_PACKET_TX : L4_U64_PACKET_RX, v); break;
-                                case 5: L4W64(tx ? L4_U64_TOTAL_BYTE_TX : L4_U64_TOTAL_BYTE_RX, v); break;
-                                case 6: L4W64(tx ? L4_U64_TOTAL_PACKET_TX : L4_U64_TOTAL_PACKET_RX, v); break;
-                                case 9: L4W32(tx ? L4_U32_TCP_FLAGS_SRC : L4_U32_TCP_FLAGS_DST, v); break;
-                                case 10: L4W32(tx ? L4_U32_EPC_0 : L4_U32_EPC_1, v); break;
-                                case 20: L4W32(tx ? L4_U32_NAT_REAL_IP_0 : L4_U32_NAT_REAL_IP_1, v); break;
-                                case 21: L4W32(tx ? L4_U32_NAT_REAL_PORT_0 : L4_U32_NAT_REAL_PORT_1, v); break;
-                                case 22: L4W32(tx ? L4_U32_GPID_0 : L4_U32_GPID_1, v); break;
-                                default: break;
-                            }
-                        } else {
-                            skip_field(bs, p2, send, w2);
-                        }
-                    }
-                    break;
-                }
-                case 13: {  // FlowPerfStats
-                    uint32_t p2 = sub;
-                    while (p2 < send) {
-                        uint64_t k2 = rd_varint(bs, p2, send);
-                        uint32_t n2 = (uint32_t)(k2 >> 3), w2 = (uint32_t)(k2 & 7);
-                        if (w2 == 0) {
-                            uint64_t v = rd_varint(bs, p2, send);
-                            if (n2 == 3) L4W8(L4_U8_L4_PROTOCOL, v);
-                            else if (n2 == 4) L4W8(L4_U8_L7_PROTOCOL, v);
-                        } else if (w2 == 2) {
-                            uint32_t l3 = (uint32_t)rd_varint(bs, p2, send);
-                            uint32_t s3 = p2, e3 = p2 + l3;
-                            p2 = e3;
-                            if (n2 == 1) {  // TCPPerfStats
-                                uint32_t p3 = s3;
-                                while (p3 < e3) {
-                                    uint64_t k3 = rd_varint(bs, p3, e3);
-                                    uint32_t n3 = (uint32_t)(k3 >> 3), w3 = (uint32_t)(k3 & 7);
-                                    if (w3 == 0) {
-                                        uint64_t v = rd_varint(bs, p3, e3);
-                                        switch (n3) {
-                                            case 3: L4W32(L4_U32_SRT_MAX, v); break;
-                                            case 4: L4W32(L4_U32_ART_MAX, v); break;
-                                            case 5: L4W32(L4_U32_RTT, v); break;
-                                            case 8: L4W32(L4_U32_SRT_SUM, v); break;
-                                            case 9: L4W32(L4_U32_ART_SUM, v); break;
-                                            case 12: L4W32(L4_U32_SRT_COUNT, v); break;
-                                            case 13: L4W32(L4_U32_ART_COUNT, v); break;
-                                            case 16: L4W32(L4_U32_RETRANS_TOTAL, v); break;
-                                            case 17: L4W32(L4_U32_SYN_COUNT, v); break;
-                                            case 18: L4W32(L4_U32_SYNACK_COUNT, v); break;
-                                            case 19: L4W32(L4_U32_CIT_MAX, v); break;
-                                            case 20: L4W32(L4_U32_CIT_SUM, v); break;
-                                            case 21: L4W32(L4_U32_CIT_COUNT, v); break;
-                                            default: break;
-                                        }
-                                    } else if (w3 == 2) {
-                                        uint32_t l4b = (uint32_t)rd_varint(bs, p3, e3);
-                                        uint32_t s4 = p3, e4 = p3 + l4b;
-                                        p3 = e4;
-                                        if (n3 == 14 || n3 == 15) {  // TcpPerfCountsPeer
-                                            bool ptx = n3 == 14;
-                                            uint32_t p4 = s4;
-                                            while (p4 < e4) {
-                                                uint64_t k4 = rd_varint(bs, p4, e4);
-                                                if ((k4 & 7) == 0) {
-                                                    uint64_t v = rd_varint(bs, p4, e4);
-                                                    uint32_t n4 = (uint32_t)(k4 >> 3);
-                                                    if (n4 == 1) L4W32(ptx ? L4_U32_RETRANS_TX : L4_U32_RETRANS_RX, v);
-                                                    else if (n4 == 2) L4W32(ptx ? L4_U32_ZERO_WIN_TX : L4_U32_ZERO_WIN_RX, v);
-                                                    else if (n4 == 3) L4W32(ptx ? L4_U32_OOO_TX : L4_U32_OOO_RX, v);
-                                                } else {
-                                                    uint32_t w4 = (uint32_t)(k4 & 7);
-                                                    skip_field(bs, p4, e4, w4);
-                                                }
-                                            }
-                                        }
-                                    } else {
-                                        skip_field(bs, p3, e3, w3);
-                                    }
-                                }
-                            } else if (n2 == 2) {  // L7PerfStats
-                                uint32_t p3 = s3;
-                                while (p3 < e3) {
-                                    uint64_t k3 = rd_varint(bs, p3, e3);
-                                    if ((k3 & 7) == 0) {
-                                        uint64_t v = rd_varint(bs, p3, e3);
-                                        switch ((uint32_t)(k3 >> 3)) {
-                                            case 1: L4W32(L4_U32_L7_REQUEST, v); break;
-                                            case 2: L4W32(L4_U32_L7_RESPONSE, v); break;
-                                            case 3: L4W32(L4_U32_L7_ERR_CLIENT, v); break;
-                                            case 4: L4W32(L4_U32_L7_ERR_SERVER, v); break;
-                                            case 5: L4W32(L4_U32_L7_ERR_TIMEOUT, v); break;
-                                            case 6: L4W32(L4_U32_L7_RRT_COUNT, v); break;
-                                            case 7: L4W64(L4_U64_L7_RRT_SUM, v); break;
-                                            case 8: L4W32(L4_U32_L7_RRT_MAX, v); break;
-                                            default: break;
-                                        }
-                                    } else {
-                                        uint32_t w3 = (uint32_t)(k3 & 7);
-                                        skip_field(bs, p3, e3, w3);
-                                    }
-                                }
-                            }
-                        } else {
-                            skip_field(bs, p2, send, w2);
-                        }
-                    }
-                    break;
-                }
-                case 26:
-                    cols.strc[(uint64_t)L4_STR_REQUEST_DOMAIN * cols.scratch_stride + rid] =
-                        STR_REF_PACK(sub, ln);
-                    break;
-                default: break;
-            }
-        } else {
-            skip_field(bs, pos, end, wt);
-        }
-    }
+    decode_l4_record(bs, offs[rid], lens[rid], rid, cols);
 }
 
 // ----------------------------------------------------------------------

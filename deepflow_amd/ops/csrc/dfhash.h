@@ -2,11 +2,17 @@
 // (dfgpu.hip, dfquery.hip, dfprofile.hip, dftrace.hip, dflog.hip, dfflow.hip), which get
 // them through dftable.h and dfseg.h. Internal linkage: each unit gets its
 // own copy. DEV is defined here and nowhere else.
+//
+// DF_HOST_BUILD compiles the same text as plain host C++ (no HIP header):
+// libdfcpu.so and the stand-alone fuzz program build the ingest decoders
+// that way.
 #pragma once
-#include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#ifndef DEV
+#ifdef DF_HOST_BUILD
+#define DEV inline
+#else
+#include <hip/hip_runtime.h>
 #define DEV __device__ __forceinline__
 #endif
 

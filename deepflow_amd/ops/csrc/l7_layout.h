@@ -157,6 +157,17 @@ enum {
 #define STATUS_CLIENT_ERROR 4u
 
 #define DICT_ID_INVALID 0xFFFFFFFFu
+// String refs carry 16 bits of length: a string keeps at most 65535 bytes.
+// Rule for the pooled columns (K4, k_pool_gather):
+//  - str_lens[c, row] is declared int16 but holds the length's UNSIGNED
+//    16-bit pattern, so 32768..65535 read negative through the declared
+//    type. Every reader reinterprets it as u16 (dfseg.h seg_pool_str,
+//    query/engine.py, executor.py, tracemap.py). Nothing is clamped to
+//    32767: the column is lossless up to the ref's own limit.
+//  - str_rowref[row] packs (pool offset, min(row total, 65535)). Only the
+//    offset is load-bearing: a row's extent is the sum of its str_lens, and
+//    a row whose pooled total exceeds 65535 still stores every byte.
+// Python twin of this rule: store/l7_schema.py, ops/ref.py pool_gather_ref.
 #define STR_REF_PACK(off, len) \
     ((((uint64_t)(off)) << 16) | ((len) > 0xFFFFu ? 0xFFFFu : (uint64_t)(len)))
 #define STR_REF_OFF(r) ((uint64_t)(r) >> 16)

@@ -23,6 +23,15 @@ def _stream() -> int:
 def decode_l7(payload: torch.Tensor, offs: torch.Tensor, lens: torch.Tensor,
               seg, base_row: int, scratch_str: torch.Tensor,
               scratch_attr: torch.Tensor) -> None:
+    """k_decode_l7. Contract on `payload`: its base is 8-byte aligned and
+    the allocation behind it reaches the next 8-byte boundary after the
+    last record -- the kernel loads the aligned 8-byte word that holds a
+    byte (ByteStream, pb_stream.h), so up to 7 bytes past the tensor's
+    nominal end are loaded and never looked at. The caching allocator
+    rounds every block to 512 bytes, which satisfies this for a whole
+    tensor; a view that ends inside a larger allocation does too.
+    Malformed records: contract at the top of csrc/l7_decode.h."""
+    assert payload.data_ptr() % 8 == 0, "payload must be 8-byte aligned"
     n = offs.numel()
     lib = native.gpu()
     native.check(lib.df_decode_l7(
@@ -36,6 +45,9 @@ def decode_l7(payload: torch.Tensor, offs: torch.Tensor, lens: torch.Tensor,
 
 def decode_l4(payload: torch.Tensor, offs: torch.Tensor, lens: torch.Tensor,
               seg, base_row: int, scratch_str: torch.Tensor) -> None:
+    """k_decode_l4. Same contract on `payload` as decode_l7: 8-byte aligned
+    base, allocation reaching the next 8-byte boundary."""
+    assert payload.data_ptr() % 8 == 0, "payload must be 8-byte aligned"
     n = offs.numel()
     lib = native.gpu()
     native.check(lib.df_decode_l4(

@@ -98,6 +98,15 @@ def cpu() -> ct.CDLL:
         lib.df_zstd_compress.restype = ct.c_int64
         lib.df_zstd_compress.argtypes = [ct.c_void_p, ct.c_uint64,
                                          ct.c_void_p, ct.c_uint64, ct.c_int]
+        # host build of the decode kernels' parsers (decode_host.cpp):
+        # df_decode_l7 / df_decode_l4 minus the stream, on host pointers
+        u64, u32, p = ct.c_uint64, ct.c_uint32, ct.c_void_p
+        lib.df_decode_l7_host.restype = ct.c_int
+        lib.df_decode_l7_host.argtypes = [p, p, p, u32, p, p, p, p, p, p,
+                                          u64, u64, u64]
+        lib.df_decode_l4_host.restype = ct.c_int
+        lib.df_decode_l4_host.argtypes = [p, p, p, u32, p, p, p, p,
+                                          u64, u64, u64]
         _cpu_lib = lib
     return _cpu_lib
 

@@ -3,7 +3,12 @@
 Used (a) by tests on GPU-less machines, (b) as the numerics oracle the GPU
 kernels are compared against (tests/test_gpu_pipeline.py), (c) by the
 device='cpu' pipeline (multi-process gloo tests). Semantics mirror
-ops/csrc/dfgpu.hip exactly; dictionary/table slot ids may differ from a
+ops/csrc/dfgpu.hip exactly, and for the decoders that holds for malformed
+records as well: decode_l7_ref and ref_l4.decode_l4_ref implement the
+malformed-record contract written at the top of ops/csrc/l7_decode.h and
+never raise on any byte string (tests/test_ingest_cases_cpu.py holds the
+twins, the host build of the kernel source and by-construction
+expectations to each other). Dictionary/table slot ids may differ from a
 concurrent GPU run under hash collisions, so cross-checks compare hydrated
 strings, not raw slot ids.
 """
@@ -16,7 +21,6 @@ import torch
 
 from ..store import l7_schema as S
 from ..store.dictionary import str_hash_py, domain_seed
-from ..wire.pb import read_varint
 
 M64 = (1 << 64) - 1
 _HEXSET = frozenset(b"0123456789abcdefABCDEF")
@@ -70,11 +74,78 @@ def _w(seg, fam, col, row, v):
         t[idx, row] = v & 0xFF
 
 
+def rd_varint_ref(mv, pos: int, end: int):
+    """Twin of pb_stream.h rd_varint -> (value, pos); value is None where
+    the message ends inside the varint or the varint exceeds 10 bytes."""
+    v = 0
+    for sh in range(0, 70, 7):
+        if pos >= end:
+            break
+        b = mv[pos]
+        pos += 1
+        v |= (b & 0x7F) << sh
+        if not b & 0x80:
+            return v & M64, pos
+    return None, pos
+
+
+def pb_fields(mv, pos: int, end: int):
+    """Walk one message [pos, end) by the malformed-record contract
+    (l7_decode.h): yields (num, 0, value, 0) for a varint field and
+    (num, 2, start, length) for a length-delimited one, skips well-formed
+    fixed32/fixed64 fields, and stops (never raises) where the contract
+    ends the message."""
+    while pos < end:
+        key, pos = rd_varint_ref(mv, pos, end)
+        if key is None:
+            return
+        num, wt = (key >> 3) & 0xFFFFFFFF, key & 7
+        if wt == 0:
+            v, pos = rd_varint_ref(mv, pos, end)
+            if v is None:
+                return
+            yield num, 0, v, 0
+        elif wt == 2:
+            ln, pos = rd_varint_ref(mv, pos, end)
+            if ln is None or ln > end - pos:
+                return
+            yield num, 2, pos, ln
+            pos += ln
+        elif wt == 1 and end - pos >= 8:
+            pos += 8
+        elif wt == 5 and end - pos >= 4:
+            pos += 4
+        else:
+            return
+
+
+_TOP_U = {9: ("u32", "request_length"), 10: ("u32", "response_length"),
+          17: ("u8", "direction_score"), 18: ("u32", "flags"),
+          19: ("u32", "captured_request_byte"),
+          20: ("u32", "captured_response_byte")}
+_HEAD_U = {1: ("u8", "l7_protocol"), 2: ("u8", "msg_type"), 5: ("u64", "rrt")}
+_BASE_S = {27: "process_kname_0", 28: "process_kname_1", 14: "ip6_0",
+           15: "ip6_1"}
+_TOP_S = {13: "version", 21: "biz_code"}
+# sub-message field -> ({varint field: column}, {string field: column})
+_SUB = {
+    11: ({}, {1: "request_type", 2: "request_domain", 3: "request_resource",
+              4: "endpoint"}),
+    12: ({1: ("u8", "response_status"), 2: ("u32", "response_code")},
+         {3: "exception_desc", 4: "response_result"}),
+    14: ({}, {1: "trace_id", 2: "span_id", 3: "parent_span_id"}),
+    15: ({3: ("u32", "request_id")},
+         {1: "service_name", 4: "x_request_id_0", 6: "http_user_agent",
+          7: "http_referer", 10: "x_request_id_1"}),
+}
+
+
 def decode_l7_ref(payload: bytes, offs, lens, seg, base_row: int,
                   sstr=None, sattr=None) -> None:
+    """Python twin of l7_decode.h decode_l7_record, malformed input
+    included: it follows the contract written there and never raises."""
     mv = memoryview(payload)
     if sstr is None:
-        import torch
         sstr = torch.zeros((S.N_STR, len(offs)), dtype=torch.int64)
         sattr = torch.zeros((2 * S.MAX_ATTRS, len(offs)), dtype=torch.int64)
     seg._last_sstr, seg._last_sattr = sstr, sattr
@@ -83,141 +154,58 @@ def decode_l7_ref(payload: bytes, offs, lens, seg, base_row: int,
         pos = int(offs[rid])
         end = pos + int(lens[rid])
         n_names = n_vals = 0
-        while pos < end:
-            key, pos = read_varint(mv, pos)
-            num, wt = key >> 3, key & 7
+
+        def wstr(col, off, ln):
+            sstr[_STR_IDX[col], rid] = S.str_ref_pack(off, ln)
+
+        for num, wt, a, ln in pb_fields(mv, pos, end):
             if wt == 0:
-                v, pos = read_varint(mv, pos)
-                if num == 9:
-                    _w(seg, "u32", "request_length", row, v)
-                elif num == 10:
-                    _w(seg, "u32", "response_length", row, v)
-                elif num == 17:
-                    _w(seg, "u8", "direction_score", row, v)
-                elif num == 18:
-                    _w(seg, "u32", "flags", row, v)
-                elif num == 19:
-                    _w(seg, "u32", "captured_request_byte", row, v)
-                elif num == 20:
-                    _w(seg, "u32", "captured_response_byte", row, v)
-            elif wt == 2:
-                ln, pos = read_varint(mv, pos)
-                sub, send = pos, pos + ln
-                pos = send
-                if num == 1:  # base
-                    p2 = sub
-                    while p2 < send:
-                        k2, p2 = read_varint(mv, p2)
-                        n2, w2 = k2 >> 3, k2 & 7
-                        if w2 == 0:
-                            v, p2 = read_varint(mv, p2)
-                            if n2 in _BASE_U:
-                                fam, col = _BASE_U[n2]
-                                _w(seg, fam, col, row, v)
-                        elif w2 == 2:
-                            l3, p2 = read_varint(mv, p2)
-                            s3, e3 = p2, p2 + l3
-                            p2 = e3
-                            if n2 == 9:  # head
-                                p3 = s3
-                                while p3 < e3:
-                                    k3, p3 = read_varint(mv, p3)
-                                    if (k3 & 7) == 0:
-                                        v, p3 = read_varint(mv, p3)
-                                        if k3 >> 3 == 1:
-                                            _w(seg, "u8", "l7_protocol", row, v)
-                                        elif k3 >> 3 == 2:
-                                            _w(seg, "u8", "msg_type", row, v)
-                                        elif k3 >> 3 == 5:
-                                            _w(seg, "u64", "rrt", row, v)
-                                    else:
-                                        p3 = e3
-                            elif n2 == 27:
-                                sstr[_STR_IDX["process_kname_0"], rid] = \
-                                    S.str_ref_pack(s3, l3)
-                            elif n2 == 28:
-                                sstr[_STR_IDX["process_kname_1"], rid] = \
-                                    S.str_ref_pack(s3, l3)
-                            elif n2 == 14:  # ip6_src (raw 16 bytes)
-                                sstr[_STR_IDX["ip6_0"], rid] = \
-                                    S.str_ref_pack(s3, l3)
-                            elif n2 == 15:  # ip6_dst
-                                sstr[_STR_IDX["ip6_1"], rid] = \
-                                    S.str_ref_pack(s3, l3)
-                        elif w2 == 1:
-                            p2 += 8
-                        elif w2 == 5:
-                            p2 += 4
-                elif num in (11, 12, 14, 15):
-                    strmap = {
-                        11: {1: "request_type", 2: "request_domain",
-                             3: "request_resource", 4: "endpoint"},
-                        12: {3: "exception_desc", 4: "response_result"},
-                        14: {1: "trace_id", 2: "span_id", 3: "parent_span_id"},
-                        15: {1: "service_name", 4: "x_request_id_0",
-                             6: "http_user_agent", 7: "http_referer",
-                             10: "x_request_id_1"},
-                    }[num]
-                    p2 = sub
-                    while p2 < send:
-                        k2, p2 = read_varint(mv, p2)
-                        n2, w2 = k2 >> 3, k2 & 7
-                        if w2 == 0:
-                            v, p2 = read_varint(mv, p2)
-                            if num == 12 and n2 == 1:
-                                _w(seg, "u8", "response_status", row, v)
-                            elif num == 12 and n2 == 2:
-                                _w(seg, "u32", "response_code", row, v)
-                            elif num == 15 and n2 == 3:
-                                _w(seg, "u32", "request_id", row, v)
-                        elif w2 == 2:
-                            l3, p2 = read_varint(mv, p2)
-                            if num == 15 and n2 == 16:
-                                if n_names < S.MAX_ATTRS:
-                                    sattr[n_names, rid] = \
-                                        S.str_ref_pack(p2, l3)
-                                n_names += 1
-                            elif num == 15 and n2 == 17:
-                                if n_vals < S.MAX_ATTRS:
-                                    sattr[S.MAX_ATTRS + n_vals, rid] = \
-                                        S.str_ref_pack(p2, l3)
-                                n_vals += 1
-                            elif num == 14 and n2 in (1, 2):
-                                # hex trace/span ids -> binary u64 cols
-                                # (pool fallback for non-hex forms)
-                                raw = bytes(mv[p2:p2 + l3])
-                                hexok = all(c in _HEXSET for c in raw)
-                                done = False
-                                if hexok and n2 == 1 and l3 == 32:
-                                    v = int(raw, 16)
-                                    _w(seg, "u64", "trace_id_hi", row,
-                                       v >> 64)
-                                    _w(seg, "u64", "trace_id_lo", row,
-                                       v & M64)
-                                    done = True
-                                elif hexok and n2 == 2 and l3 == 16:
-                                    _w(seg, "u64", "span_id_b", row,
-                                       int(raw, 16))
-                                    done = True
-                                if not done:
-                                    sstr[_STR_IDX[strmap[n2]], rid] = \
-                                        S.str_ref_pack(p2, l3)
-                            elif n2 in strmap:
-                                sstr[_STR_IDX[strmap[n2]], rid] = \
-                                    S.str_ref_pack(p2, l3)
-                            p2 += l3
-                        elif w2 == 1:
-                            p2 += 8
-                        elif w2 == 5:
-                            p2 += 4
-                elif num == 13:
-                    sstr[_STR_IDX["version"], rid] = S.str_ref_pack(sub, ln)
-                elif num == 21:
-                    sstr[_STR_IDX["biz_code"], rid] = S.str_ref_pack(sub, ln)
-            elif wt == 1:
-                pos += 8
-            elif wt == 5:
-                pos += 4
+                if num in _TOP_U:
+                    _w(seg, *_TOP_U[num], row, a)
+            elif num == 1:  # AppProtoLogsBaseInfo
+                for n2, w2, a2, l2 in pb_fields(mv, a, a + ln):
+                    if w2 == 0:
+                        if n2 in _BASE_U:
+                            _w(seg, *_BASE_U[n2], row, a2)
+                    elif n2 == 9:  # AppProtoHead
+                        for n3, w3, a3, _ in pb_fields(mv, a2, a2 + l2):
+                            if w3 == 0 and n3 in _HEAD_U:
+                                _w(seg, *_HEAD_U[n3], row, a3)
+                    elif n2 in _BASE_S:
+                        wstr(_BASE_S[n2], a2, l2)
+            elif num in _SUB:
+                umap, smap = _SUB[num]
+                for n2, w2, a2, l2 in pb_fields(mv, a, a + ln):
+                    if w2 == 0:
+                        if n2 in umap:
+                            _w(seg, *umap[n2], row, a2)
+                    elif num == 15 and n2 == 16:
+                        if n_names < S.MAX_ATTRS:
+                            sattr[n_names, rid] = S.str_ref_pack(a2, l2)
+                        n_names += 1
+                    elif num == 15 and n2 == 17:
+                        if n_vals < S.MAX_ATTRS:
+                            sattr[S.MAX_ATTRS + n_vals, rid] = \
+                                S.str_ref_pack(a2, l2)
+                        n_vals += 1
+                    elif num == 14 and n2 == 1 and l2 == 32 and \
+                            hex_parse64_py(bytes(mv[a2:a2 + 16])) is not None \
+                            and hex_parse64_py(
+                                bytes(mv[a2 + 16:a2 + 32])) is not None:
+                        # hex trace/span ids -> binary u64 cols (pool
+                        # fallback for non-hex forms)
+                        _w(seg, "u64", "trace_id_hi", row,
+                           hex_parse64_py(bytes(mv[a2:a2 + 16])))
+                        _w(seg, "u64", "trace_id_lo", row,
+                           hex_parse64_py(bytes(mv[a2 + 16:a2 + 32])))
+                    elif num == 14 and n2 == 2 and l2 == 16 and \
+                            hex_parse64_py(bytes(mv[a2:a2 + 16])) is not None:
+                        _w(seg, "u64", "span_id_b", row,
+                           hex_parse64_py(bytes(mv[a2:a2 + 16])))
+                    elif n2 in smap:
+                        wstr(smap[n2], a2, l2)
+            elif num in _TOP_S:
+                wstr(_TOP_S[num], a, ln)
         na = min(n_names, n_vals, S.MAX_ATTRS)
         seg.attr_cnt[row] = na
 
@@ -357,7 +345,9 @@ def pool_gather_ref(payload: bytes, seg, pool_cols, base_row: int, n: int,
             off = r >> 16
             pool[dst:dst + ln] = np.frombuffer(payload[off:off + ln],
                                                dtype=np.uint8)
-            seg.str_lens[ci, base_row + i] = ln
+            # u16 bit pattern in the int16 column (l7_schema.py, str_lens)
+            seg.str_lens[ci, base_row + i] = ln - (1 << 16) \
+                if ln >= (1 << 15) else ln
             dst += ln
         seg.str_rowref[base_row + i] = S.str_ref_pack(dst0, dst - dst0)
 

@@ -1,79 +1,73 @@
-"""CPU reference for the L4 (TaggedFlow) decode + network.1s rollup.
+"""CPU reference for the L4 (TaggedFlow) decode.
 
-Uses the generic pb decoder as an independent oracle (unlike ref.py's
-hand-rolled L7 parser) — the GPU kernel is validated against a completely
-separate implementation path.
+Python twin of ops/csrc/l4_decode.h decode_l4_record: the same field ->
+column tables walked with ref.pb_fields, so it follows the malformed-record
+contract (top of l7_decode.h) and never raises on any byte string. Like the
+kernel it writes a column only when its field is on the wire and decodes
+only the first Flow of a record. The independent check of both is
+tests/ingest_cases.py, whose expectations are known by construction.
 """
 from __future__ import annotations
 
-from typing import Dict, List
-
 from ..store import l4_schema as L4
 from ..store import l7_schema as S
-from ..wire import pb, flow_log
-from ..wire.pb import read_varint
+from .ref import pb_fields, rd_varint_ref
 
 M64 = (1 << 64) - 1
 
 _U64 = {c: i for i, c in enumerate(L4.U64_COLS)}
 _U32 = {c: i for i, c in enumerate(L4.U32_COLS)}
 _U8 = {c: i for i, c in enumerate(L4.U8_COLS)}
+_STR = {c: i for i, c in enumerate(L4.STR_COLS)}
+
+# varint field number -> column, per message (flow_log.proto)
+_FLOW = {5: "flow_id", 6: "start_time", 7: "end_time", 8: "duration",
+         10: "vlan", 11: "eth_type", 14: "close_type", 15: "signal_source",
+         16: "is_active_service", 18: "is_new_flow", 19: "tap_side",
+         25: "direction_score"}
+_FLOW_KEY = {1: "vtap_id", 2: "tap_type", 4: "mac_src", 5: "mac_dst",
+             6: "ip4_0", 7: "ip4_1", 10: "client_port", 11: "server_port",
+             12: "protocol"}
+# FlowMetricsPeer: (src column, dst column)
+_PEER = {1: ("byte_tx", "byte_rx"), 2: ("l3_byte_tx", "l3_byte_rx"),
+         3: ("l4_byte_tx", "l4_byte_rx"), 4: ("packet_tx", "packet_rx"),
+         5: ("total_byte_tx", "total_byte_rx"),
+         6: ("total_packet_tx", "total_packet_rx"),
+         9: ("tcp_flags_bit_0", "tcp_flags_bit_1"),
+         10: ("l3_epc_id_0", "l3_epc_id_1"),
+         20: ("nat_real_ip_0", "nat_real_ip_1"),
+         21: ("nat_real_port_0", "nat_real_port_1"),
+         22: ("gprocess_id_0", "gprocess_id_1")}
+_PERF = {3: "l4_protocol", 4: "l7_protocol"}
+_TCP = {3: "srt_max", 4: "art_max", 5: "rtt", 8: "srt_sum", 9: "art_sum",
+        12: "srt_count", 13: "art_count", 16: "retrans_total",
+        17: "syn_count", 18: "synack_count", 19: "cit_max", 20: "cit_sum",
+        21: "cit_count"}
+# TcpPerfCountsPeer: (tx column, rx column)
+_TCP_PEER = {1: ("retrans_tx", "retrans_rx"),
+             2: ("zero_win_tx", "zero_win_rx"), 3: ("ooo_tx", "ooo_rx")}
+_L7PERF = {1: "l7_request", 2: "l7_response", 3: "l7_err_client",
+           4: "l7_err_server", 5: "l7_err_timeout", 6: "l7_rrt_count",
+           7: "l7_rrt_sum", 8: "l7_rrt_max"}
 
 
-def _find_str_refs(mv: memoryview, pos: int, end: int) -> Dict[int, tuple]:
-    """Byte ranges of the pooled L4 strings: Flow.request_domain
-    (path 1 -> 26) and FlowKey.ip6_src/dst (path 1 -> 1 -> 8/9).
-    -> {str_col_idx: (off, len)}"""
-    out: Dict[int, tuple] = {}
-    while pos < end:
-        key, pos = read_varint(mv, pos)
-        num, wt = key >> 3, key & 7
-        if num == 1 and wt == 2:
-            ln, pos = read_varint(mv, pos)
-            fend = pos + ln
-            while pos < fend:
-                k2, pos = read_varint(mv, pos)
-                n2, w2 = k2 >> 3, k2 & 7
-                if w2 == 2:
-                    l2, pos = read_varint(mv, pos)
-                    if n2 == 26:
-                        out[L4.STR_COLS.index("request_domain")] = (pos, l2)
-                    elif n2 == 1:  # FlowKey
-                        p3, e3 = pos, pos + l2
-                        while p3 < e3:
-                            k3, p3 = read_varint(mv, p3)
-                            n3, w3 = k3 >> 3, k3 & 7
-                            if w3 == 2:
-                                l3, p3 = read_varint(mv, p3)
-                                if n3 == 8:
-                                    out[L4.STR_COLS.index("ip6_0")] = (p3, l3)
-                                elif n3 == 9:
-                                    out[L4.STR_COLS.index("ip6_1")] = (p3, l3)
-                                p3 += l3
-                            elif w3 == 0:
-                                _, p3 = read_varint(mv, p3)
-                            elif w3 == 1:
-                                p3 += 8
-                            else:
-                                p3 += 4
-                    pos += l2
-                elif w2 == 0:
-                    _, pos = read_varint(mv, pos)
-                elif w2 == 1:
-                    pos += 8
-                else:
-                    pos += 4
-            return out
-        if wt == 0:
-            _, pos = read_varint(mv, pos)
-        elif wt == 2:
-            ln, pos = read_varint(mv, pos)
-            pos += ln
-        elif wt == 1:
-            pos += 8
-        else:
-            pos += 4
-    return out
+def _w(seg, row, col, v):
+    if col in _U64:
+        v &= M64
+        seg.u64[_U64[col], row] = v - (1 << 64) if v >= (1 << 63) else v
+    elif col in _U32:
+        v &= 0xFFFFFFFF
+        seg.u32[_U32[col], row] = v - (1 << 32) if v >= (1 << 31) else v
+    else:
+        seg.u8[_U8[col], row] = v & 0xFF
+
+
+def _varints(mv, seg, row, pos, end, table, side=None):
+    """Store the mapped varint fields of a message without sub-messages."""
+    for num, wt, a, _ in pb_fields(mv, pos, end):
+        if wt == 0 and num in table:
+            col = table[num]
+            _w(seg, row, col if side is None else col[side], a)
 
 
 def decode_l4_ref(payload: bytes, offs, lens, seg, base_row: int,
@@ -84,92 +78,47 @@ def decode_l4_ref(payload: bytes, offs, lens, seg, base_row: int,
         sstr = torch.zeros((L4.N_STR, len(offs)), dtype=torch.int64)
     for rid in range(len(offs)):
         row = base_row + rid
-        off, ln = int(offs[rid]), int(lens[rid])
-        d = pb.decode(mv[off:off + ln], flow_log.TAGGED_FLOW)
-        f = d.get("flow", {})
-        fk = f.get("flow_key", {})
-        src = f.get("metrics_peer_src", {})
-        dst = f.get("metrics_peer_dst", {})
-        perf = f.get("perf_stats", {})
-        tcp = perf.get("tcp", {})
-        l7 = perf.get("l7", {})
-        ptx = tcp.get("counts_peer_tx", {})
-        prx = tcp.get("counts_peer_rx", {})
-
-        def w64(col, v):
-            seg.u64[_U64[col], row] = (v & M64) - (1 << 64) \
-                if (v & M64) >= (1 << 63) else v & M64
-
-        def w32(col, v):
-            v &= 0xFFFFFFFF
-            seg.u32[_U32[col], row] = v - (1 << 32) if v >= (1 << 31) else v
-
-        def w8(col, v):
-            seg.u8[_U8[col], row] = v & 0xFF
-
-        w64("start_time", f.get("start_time", 0))
-        w64("end_time", f.get("end_time", 0))
-        w64("duration", f.get("duration", 0))
-        w64("flow_id", f.get("flow_id", 0))
-        w64("mac_src", fk.get("mac_src", 0))
-        w64("mac_dst", fk.get("mac_dst", 0))
-        for name, m in (("tx", src), ("rx", dst)):
-            w64(f"byte_{name}", m.get("byte_count", 0))
-            w64(f"l3_byte_{name}", m.get("l3_byte_count", 0))
-            w64(f"l4_byte_{name}", m.get("l4_byte_count", 0))
-            w64(f"packet_{name}", m.get("packet_count", 0))
-            w64(f"total_byte_{name}", m.get("total_byte_count", 0))
-            w64(f"total_packet_{name}", m.get("total_packet_count", 0))
-        w64("l7_rrt_sum", l7.get("rrt_sum", 0))
-        w32("vtap_id", fk.get("vtap_id", 0))
-        w32("ip4_0", fk.get("ip_src", 0))
-        w32("ip4_1", fk.get("ip_dst", 0))
-        w32("l3_epc_id_0", src.get("l3_epc_id", 0))
-        w32("l3_epc_id_1", dst.get("l3_epc_id", 0))
-        w32("client_port", fk.get("port_src", 0))
-        w32("server_port", fk.get("port_dst", 0))
-        w32("tcp_flags_bit_0", src.get("tcp_flags", 0))
-        w32("tcp_flags_bit_1", dst.get("tcp_flags", 0))
-        w32("rtt", tcp.get("rtt", 0))
-        for p in ("srt", "art", "cit"):
-            w32(f"{p}_sum", tcp.get(f"{p}_sum", 0))
-            w32(f"{p}_count", tcp.get(f"{p}_count", 0))
-            w32(f"{p}_max", tcp.get(f"{p}_max", 0))
-        w32("retrans_tx", ptx.get("retrans_count", 0))
-        w32("retrans_rx", prx.get("retrans_count", 0))
-        w32("zero_win_tx", ptx.get("zero_win_count", 0))
-        w32("zero_win_rx", prx.get("zero_win_count", 0))
-        w32("ooo_tx", ptx.get("ooo_count", 0))
-        w32("ooo_rx", prx.get("ooo_count", 0))
-        w32("syn_count", tcp.get("syn_count", 0))
-        w32("synack_count", tcp.get("synack_count", 0))
-        w32("retrans_total", tcp.get("total_retrans_count", 0))
-        w32("l7_request", l7.get("request_count", 0))
-        w32("l7_response", l7.get("response_count", 0))
-        w32("l7_rrt_count", l7.get("rrt_count", 0))
-        w32("l7_rrt_max", l7.get("rrt_max", 0))
-        w32("l7_err_client", l7.get("err_client_count", 0))
-        w32("l7_err_server", l7.get("err_server_count", 0))
-        w32("l7_err_timeout", l7.get("err_timeout", 0))
-        w32("gprocess_id_0", src.get("gpid", 0))
-        w32("gprocess_id_1", dst.get("gpid", 0))
-        w32("nat_real_ip_0", src.get("real_ip", 0))
-        w32("nat_real_ip_1", dst.get("real_ip", 0))
-        w32("nat_real_port_0", src.get("real_port", 0))
-        w32("nat_real_port_1", dst.get("real_port", 0))
-        w32("vlan", f.get("vlan", 0))
-        w32("eth_type", f.get("eth_type", 0))
-        gids = f.get("acl_gids", [])
-        w32("acl_gid", gids[0] if gids else 0)
-        w8("close_type", f.get("close_type", 0))
-        w8("tap_side", f.get("tap_side", 0))
-        w8("tap_type", fk.get("tap_type", 0))
-        w8("protocol", fk.get("proto", 0))
-        w8("l4_protocol", perf.get("l4_protocol", 0))
-        w8("l7_protocol", perf.get("l7_protocol", 0))
-        w8("signal_source", f.get("signal_source", 0))
-        w8("is_new_flow", f.get("is_new_flow", 0))
-        w8("is_active_service", f.get("is_active_service", 0))
-        w8("direction_score", f.get("direction_score", 0))
-        for sc, (roff, rlen) in _find_str_refs(mv, off, off + ln).items():
-            sstr[sc, rid] = S.str_ref_pack(roff, rlen)
+        pos = int(offs[rid])
+        end = pos + int(lens[rid])
+        flow = None
+        for num, wt, a, ln in pb_fields(mv, pos, end):
+            if num == 1 and wt == 2:  # first Flow only
+                flow = (a, a + ln)
+                break
+        if flow is None:
+            continue
+        for num, wt, a, ln in pb_fields(mv, *flow):
+            if wt == 0:
+                if num in _FLOW:
+                    _w(seg, row, _FLOW[num], a)
+            elif num == 1:  # FlowKey
+                for n2, w2, a2, l2 in pb_fields(mv, a, a + ln):
+                    if w2 == 0:
+                        if n2 in _FLOW_KEY:
+                            _w(seg, row, _FLOW_KEY[n2], a2)
+                    elif n2 in (8, 9):  # ip6_src/dst, raw 16 bytes
+                        sstr[_STR["ip6_0" if n2 == 8 else "ip6_1"], rid] = \
+                            S.str_ref_pack(a2, l2)
+            elif num in (2, 3):  # FlowMetricsPeer src/dst
+                _varints(mv, seg, row, a, a + ln, _PEER, side=num - 2)
+            elif num == 13:  # FlowPerfStats
+                for n2, w2, a2, l2 in pb_fields(mv, a, a + ln):
+                    if w2 == 0:
+                        if n2 in _PERF:
+                            _w(seg, row, _PERF[n2], a2)
+                    elif n2 == 1:  # TCPPerfStats
+                        for n3, w3, a3, l3 in pb_fields(mv, a2, a2 + l2):
+                            if w3 == 0:
+                                if n3 in _TCP:
+                                    _w(seg, row, _TCP[n3], a3)
+                            elif n3 in (14, 15):  # TcpPerfCountsPeer tx/rx
+                                _varints(mv, seg, row, a3, a3 + l3,
+                                         _TCP_PEER, side=n3 - 14)
+                    elif n2 == 2:  # L7PerfStats
+                        _varints(mv, seg, row, a2, a2 + l2, _L7PERF)
+            elif num == 24:  # acl_gids (packed repeated u32): keep first
+                v, _ = rd_varint_ref(mv, a, a + ln)
+                if v is not None:
+                    _w(seg, row, "acl_gid", v)
+            elif num == 26:
+                sstr[_STR["request_domain"], rid] = S.str_ref_pack(a, ln)

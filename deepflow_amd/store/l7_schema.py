@@ -87,6 +87,13 @@ N_DID = len(DID_COLS)
 N_KG = len(KG_COLS)
 
 
+# String refs carry 16 bits of length, so a string keeps at most 65535
+# bytes. Rule for the pooled columns (l7_layout.h, same words): the int16
+# str_lens column holds the length's unsigned 16-bit pattern (32768..65535
+# read negative through the dtype; readers view it as uint16, nothing is
+# clamped to 32767), and str_rowref packs (pool offset, min(row total,
+# 65535)) of which only the offset is load-bearing -- a row's extent is
+# the sum of its str_lens.
 def str_ref_pack(off: int, ln: int) -> int:
     return (off << 16) | min(ln, 0xFFFF)
 
